@@ -13,7 +13,7 @@ whole-shard CSR resident in HBM -> RCCL all-reduce of (rows, nnz, max index)
 for the global NumCol.  Nothing is cached between steps: every step re-reads
 and re-parses the text.  Total work is fixed as N grows (strong scaling).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
        torchrun --nproc-per-node N bench.py --gpus N ...
        dmlc-submit --cluster local --num-workers N --gpus-per-node N python bench.py --gpus N
          (the dmlc tracker assigns ranks and bootstraps the RCCL/gloo group)
@@ -24,6 +24,11 @@ through ``dmlc-submit --cluster local`` (reference
 `tracker/dmlc_tracker/local.py:47-72`), forwards their output (rank 0's JSON
 line) and exits with their status.  Every rank checks that the world it joined
 has exactly ``--gpus`` ranks.
+
+A plain run sets up the dataset, warms up, times ``--steps`` steps and prints
+the result line.  ``--dump-outputs DIR`` also writes the last timed step's CSR
+arrays (``dump_outputs``); ``--full`` adds the all-reduce probe of a multi-rank
+run, the one measurement beside the headline figure.
 """
 from __future__ import annotations
 
@@ -112,7 +117,15 @@ def parse_args():
     ap.add_argument("--share-gpu", action="store_true",
                     help="every rank uses GPU 0 (gloo control plane): rehearses the multi-rank "
                          "GPU branch on a one-GPU box (RCCL refuses two ranks on one device)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed (this rank's "
+                         "CSR arrays, or a fixed seeded sample of the large ones) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beside the headline figure (the all-reduce "
+                         "bus-bandwidth probe of a multi-rank run)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1 (the result is the mean of the timed steps)")
     if args.rows <= 0:
         args.rows = FORMATS[args.format]["rows"]
     return args
@@ -228,6 +241,46 @@ def allreduce_probe(dist, cdev, world: int, sizes=(4 << 20, 256 << 20), iters: i
     return out
 
 
+DUMP_MAX_ELEMS = 1 << 20  # per array: at most 7 arrays x 8 B x 2^20 = 59 MB per rank
+
+
+def dump_outputs(dirpath: str, rank: int, tensors, counts) -> None:
+    """Write the last timed step's outputs as ``<name>.npy`` (rank 0) or
+    ``<name>_rank<r>.npy``: ``counts`` = this rank's (rows, nnz, max index,
+    input bytes) and every array of its device CSR / byte-CSR.  Integer arrays
+    are stored as float64 (exact below 2^53), float and byte arrays as float32.
+    An array of more than DUMP_MAX_ELEMS elements is sampled at DUMP_MAX_ELEMS
+    positions drawn once from a generator seeded with 0 and sorted, so the same
+    arguments give the same positions in every run and every build."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirpath, exist_ok=True)
+    suffix = "" if rank == 0 else f"_rank{rank}"
+    np.save(os.path.join(dirpath, f"counts{suffix}.npy"), np.asarray(counts, dtype=np.float64))
+    signed = {torch.uint16: torch.int16, torch.uint32: torch.int32, torch.uint64: torch.int64}
+    for name in sorted(tensors):
+        t = tensors[name]
+        if not isinstance(t, torch.Tensor):
+            continue
+        t = t.reshape(-1)
+        bits = 8 * t.element_size()
+        unsigned = t.dtype in signed
+        if unsigned:  # torch indexes and converts the signed view only
+            t = t.view(signed[t.dtype])
+        if t.numel() > DUMP_MAX_ELEMS:
+            pos = np.sort(np.random.default_rng(0).integers(0, t.numel(), size=DUMP_MAX_ELEMS))
+            t = t.index_select(0, torch.from_numpy(pos).to(t.device))
+        if t.dtype.is_floating_point or t.dtype == torch.uint8:
+            a = t.to(torch.float32)
+        else:
+            a = t.to(torch.int64)
+            if unsigned and bits < 64:
+                a = a & ((1 << bits) - 1)  # undo the signed view
+            a = a.to(torch.float64)
+        np.save(os.path.join(dirpath, f"{name}{suffix}.npy"), a.cpu().numpy())
+
+
 def main():
     args = parse_args()
     if args.gpus < 1:
@@ -297,6 +350,7 @@ def main():
             parser.before_first()
             b = parser.read_all()
             local["rows"], local["bytes"] = b["size"], parser.partition_bytes
+            local["outputs"] = lambda: dio.GPURecordIO.to_torch(b)
             return b["size"], b["bytes"], 0, parser.partition_bytes
     elif use_gpu and args.mode == "cache":
         extra = {"label_column": 0} if args.format == "csv" else {}
@@ -319,6 +373,7 @@ def main():
         def step():
             parser.load(csr)
             local["rows"], local["bytes"] = csr.rows, parser.bytes
+            local["outputs"] = lambda: data.csr_to_torch(csr)
             return csr.rows, csr.nnz, csr.max_index, parser.bytes
     elif use_gpu:
         extra = {"label_column": 0} if args.format == "csv" else {}
@@ -343,6 +398,7 @@ def main():
             csr.clear()
             parser.parse_all(csr)
             local["rows"], local["bytes"] = csr.rows, parser.partition_bytes
+            local["outputs"] = lambda: data.csr_to_torch(csr)
             return csr.rows, csr.nnz, csr.max_index, parser.partition_bytes
     elif args.format == "recordio":
         from dmlc_core_amd import io as dio
@@ -391,6 +447,8 @@ def main():
     barrier()
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, local["outputs"]() if "outputs" in local else {}, r)
     # per-rank view (rows, bytes, own time, host waits) gathered to every rank
     st = parser.stats() if use_gpu and args.mode != "cache" else {}
     mine = torch.tensor([rank, local["rows"], local["bytes"], elapsed,
@@ -426,7 +484,7 @@ def main():
     rec.update(parser_record(st))
     reduced = reduce_across_ranks(rec, device=cdev)
     probe = (allreduce_probe(dist, cdev, world, iters=5 if cdev.type == "cuda" else 2)
-             if world > 1 else None)
+             if args.full and world > 1 else None)
     with MetricsLogger() as ml:
         ml.log("ingest", steps=args.steps, **rec)
         if rank == 0:

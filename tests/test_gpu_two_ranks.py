@@ -49,7 +49,7 @@ def test_bench_share_gpu_two_ranks(tmp_path, mode):
     JSON line a SCALE run prints, with rows summing to the dataset."""
     env = dict(os.environ, PYTHONPATH=ROOT, DMLC_HEARTBEAT_PERIOD="1")
     cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu",
-           "--steps", "2", "--warmup", "1", "--rows", "120000", "--mode", mode,
+           "--full", "--steps", "2", "--warmup", "1", "--rows", "120000", "--mode", mode,
            "--data-dir", str(tmp_path / "bench")]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-5000:]
@@ -74,7 +74,7 @@ def test_bench_share_gpu_eight_ranks(tmp_path):
     than its budget -- 8 ranks never lock 8 x the host budget."""
     env = dict(os.environ, PYTHONPATH=ROOT, DMLC_HEARTBEAT_PERIOD="1")
     cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "8", "--share-gpu",
-           "--steps", "2", "--warmup", "1", "--rows", "400000",
+           "--full", "--steps", "2", "--warmup", "1", "--rows", "400000",
            "--data-dir", str(tmp_path / "bench")]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-5000:]
@@ -106,7 +106,7 @@ def test_bench_two_gpus_over_rccl(tmp_path, mode):
         pytest.skip("needs >= 2 GPUs (RCCL at world 2)")
     env = dict(os.environ, PYTHONPATH=ROOT, DMLC_HEARTBEAT_PERIOD="1")
     cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "2",
-           "--steps", "2", "--warmup", "1", "--rows", "200000", "--mode", mode,
+           "--full", "--steps", "2", "--warmup", "1", "--rows", "200000", "--mode", mode,
            "--data-dir", str(tmp_path / "bench")]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=280, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-5000:]
