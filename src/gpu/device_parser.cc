@@ -30,7 +30,6 @@
 #include <unistd.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cstring>
 #include <deque>
 #include <memory>
@@ -42,6 +41,7 @@
 #include "../io/uri_spec.h"
 #include "./host_wait.h"
 #include "./kernels.h"
+#include "./tile_pipeline.h"
 #include "./zero_copy_source.h"
 
 namespace dmlc {
@@ -198,22 +198,12 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
       parsed_.back()->Record(compute_->get());
     }
     tiles_.Reserve(LineIndexTiles(cfg_.chunk_bytes) * sizeof(uint64_t));
-    tcounts_.Reserve(TileScratchWords(TileCount(cfg_.chunk_bytes)) * sizeof(uint64_t));
-    tflags_.Reserve(TileScratchWords(TileCount(cfg_.chunk_bytes)) * sizeof(uint32_t));
-    tmasks_.Reserve(TileMaskWords(TileCount(cfg_.chunk_bytes)) * sizeof(uint32_t));
-    meta_.Reserve(2 * sizeof(ChunkMeta));
+    // with hbm_cache a second C1/C2 scratch set: the next resident chunk's
+    // count + scan runs on its own stream, concurrently with the current fill
+    // (PrelaunchCount)
+    pre_.Init(2 * sizeof(ChunkMeta), /*with_next=*/cfg_.hbm_cache);
+    pre_.cur.Reserve(TileCount(cfg_.chunk_bytes), /*with_masks=*/true);
     hmeta_.Reserve(2 * sizeof(ChunkMeta));
-    hmap_.Reserve(sizeof(ChunkMeta), /*mapped=*/true);
-    std::memset(hmap_.get(), 0, sizeof(ChunkMeta));  // WaitMapped polls its pad word
-    if (cfg_.hbm_cache) {
-      // second C1/C2 scratch set: the next resident chunk's count + scan runs
-      // on its own stream, concurrently with the current fill (PrelaunchCount)
-      count_stream_.reset(new Stream());
-      pre_done_.reset(new Event());
-      meta_next_.Reserve(2 * sizeof(ChunkMeta));
-      hmap_next_.Reserve(sizeof(ChunkMeta), /*mapped=*/true);
-      std::memset(hmap_next_.get(), 0, sizeof(ChunkMeta));
-    }
     slots_.Reserve(std::max<size_t>(kMaxPartialBlocks, TileScratchSlots(TileCount(cfg_.chunk_bytes))) *
                    sizeof(MetaPartial));
     iter_.set_max_capacity(static_cast<size_t>(cfg_.pinned_slots));
@@ -241,7 +231,7 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
     // destructors never throw, so errors are ignored here
     if (copy_) (void)hipStreamSynchronize(copy_->get());
     if (compute_) (void)hipStreamSynchronize(compute_->get());
-    if (count_stream_) (void)hipStreamSynchronize(count_stream_->get());
+    if (pre_.stream) (void)hipStreamSynchronize(pre_.stream->get());
     for (auto& f : inflight_) {
       if (f.slot != nullptr) iter_.Recycle(&f.slot);
     }
@@ -518,7 +508,7 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
         // line on the zero-copy path -- must stay its own chunk).  The merged
         // size doubles per chunk from replay_first_bytes: the first chunk's count +
         // scan is the only one not hidden behind a previous chunk's fill (the
-        // next count runs on count_stream_ meanwhile, and next to a fill it
+        // next count runs on its own stream meanwhile, and next to a fill it
         // takes about half the fill's time per byte: 2x keeps it hidden)
         merge_cap_ = merge_cap_ == 0
                          ? (cfg_.replay_first_bytes != 0 ? cfg_.replay_first_bytes
@@ -622,7 +612,7 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
   void DrainInflight(bool keep_prelaunch = false) {
     copy_->Synchronize();
     compute_->Synchronize();
-    if (!keep_prelaunch) DropPrelaunch();
+    if (!keep_prelaunch) pre_.Drop();
     while (!inflight_.empty()) {
       if (inflight_.front().slot != nullptr) iter_.Recycle(&inflight_.front().slot);
       inflight_.pop_front();
@@ -639,24 +629,16 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
   /*! \brief the ChunkMeta a kernel wrote into mapped pinned memory (synchronises) */
   ChunkMeta WaitMapped(ChunkMeta* hm) {
     const double t0 = GetTime();
-    // the publishing kernel raises hm->pad last (after a system fence): poll
-    // it rather than pay a blocking stream synchronise per chunk -- a short
-    // spin, then short sleeps (host_wait.h); bounded, so a kernel that never
-    // publishes (a fault) still surfaces through the sync
-    volatile unsigned* flag = &hm->pad;
-    const bool seen = WaitHostFlag(flag, cfg_.wait_spin_us, 0.05, &wait_stats_);
-    if (!seen) {
+    // polled rather than a blocking stream synchronise per chunk; bounded, so
+    // a kernel that never publishes (a fault) still surfaces through the sync
+    const ChunkMeta v = TakePublished(hm, cfg_.wait_spin_us, 0.05, &wait_stats_, [this] {
       compute_->Synchronize();
-      if (count_stream_) count_stream_->Synchronize();
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
+      if (pre_.stream) pre_.stream->Synchronize();
+    });
     stats_.wait_gpu_sec += GetTime() - t0;
     stats_.waits_spun = wait_stats_.spun;
     stats_.waits_slept = wait_stats_.slept;
     stats_.waits_timed_out = wait_stats_.timed_out;
-    ChunkMeta v;
-    std::memcpy(&v, const_cast<const ChunkMeta*>(hm), sizeof(v));
-    *flag = 0;  // re-armed before the next publishing kernel is launched
     return v;
   }
 
@@ -676,9 +658,7 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
   /*! \brief per-chunk scratch for a chunk of nbytes (chunks may exceed chunk_bytes) */
   void EnsureScratch(size_t nbytes) {
     const size_t tiles = TileCount(nbytes);
-    tcounts_.Reserve(TileScratchWords(tiles) * sizeof(uint64_t));
-    tflags_.Reserve(TileScratchWords(tiles) * sizeof(uint32_t));
-    tmasks_.Reserve(TileMaskWords(tiles) * sizeof(uint32_t));
+    pre_.cur.Reserve(tiles, /*with_masks=*/true);
     slots_.Reserve(std::max<size_t>(kMaxPartialBlocks, TileScratchSlots(tiles)) * sizeof(MetaPartial));
     tiles_.Reserve(LineIndexTiles(nbytes) * sizeof(uint64_t));
   }
@@ -687,6 +667,30 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
     lines_.Reserve((nlines + 1) * sizeof(uint32_t));
     info_.Reserve((nlines + 1) * sizeof(uint64_t));
     partials_.Reserve((ScanPartials(nlines) + 2) * sizeof(uint64_t));
+  }
+
+  /*! \brief the fill target over out's arrays: rows [row_base, row_limit) and
+   *  entries [nnz_base, nnz_limit) may be written */
+  FillTarget<IndexType> MakeFillTarget(DeviceCSR<IndexType>* out, size_t row_base, size_t nnz_base,
+                                       size_t row_limit, size_t nnz_limit, bool with_qid) {
+    FillTarget<IndexType> tgt;
+    tgt.offset = out->offset();
+    tgt.label = out->label();
+    // an empty target has no weight column (only the one-pass fill meets one:
+    // PrepareOutput has reserved >= 1 row -- its first-chunk Reserve asks for
+    // nrows * scale + 1, later chunks follow written rows)
+    tgt.weight = out->weight_capacity() >= out->row_capacity() && out->row_capacity() != 0
+                     ? out->weight()
+                     : nullptr;
+    tgt.qid = with_qid ? out->qid() : nullptr;
+    tgt.field = tcfg_.format == TextFormat::kLibFM ? out->field() : nullptr;
+    tgt.index = out->index();
+    tgt.value = out->value();
+    tgt.row_base = row_base;
+    tgt.nnz_base = nnz_base;
+    tgt.row_limit = row_limit;
+    tgt.nnz_limit = nnz_limit;
+    return tgt;
   }
 
   /*! \brief grow the output for this chunk and build the fill target */
@@ -707,19 +711,31 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
       out->EnableQid(s);
       out->has_qid_ = true;
     }
-    FillTarget<IndexType> tgt;
-    tgt.offset = out->offset();
-    tgt.label = out->label();
-    tgt.weight = out->weight_capacity() >= out->row_capacity() ? out->weight() : nullptr;
-    tgt.qid = out->has_qid_ ? out->qid() : nullptr;
-    tgt.field = libfm ? out->field() : nullptr;
-    tgt.index = out->index();
-    tgt.value = out->value();
-    tgt.row_base = row_base;
-    tgt.nnz_base = nnz_base;
-    tgt.row_limit = row_base + plan.nrows;
-    tgt.nnz_limit = nnz_base + plan.nnz;
-    return tgt;
+    return MakeFillTarget(out, row_base, nnz_base, row_base + plan.nrows, nnz_base + plan.nnz,
+                          out->has_qid_);
+  }
+
+  /*! \brief the tile pipeline's count + scan (LibSVM / LibFM C1 + C2, or CSV S1 + scan) */
+  void LaunchCountScan(const char* text, size_t nbytes, const TileScratchSet& set, hipStream_t s) {
+    uint64_t* counts = set.counts.get<uint64_t>();
+    uint32_t* flags = set.flags.get<uint32_t>();
+    uint32_t* masks = set.masks.get<uint32_t>();
+    if (tcfg_.format == TextFormat::kCSV) {
+      LaunchCsvTileCount(text, nbytes, tcfg_.label_column, tcfg_.weight_column, tcfg_.delimiter,
+                         counts, flags, masks, s);
+      LaunchTileScanRaw(counts, flags, TileCount(nbytes), set.dmeta(), set.hmeta(), s);
+    } else {
+      LaunchTileCountScan(text, nbytes, counts, flags, masks, set.dmeta(), set.hmeta(), s);
+    }
+  }
+
+  /*! \brief count + scan of this chunk into the current scratch set: adopt the
+   *  prelaunched set when it holds this chunk (queued behind the previous
+   *  fill), else launch them now */
+  void CountScanCurrent(const char* text, size_t nbytes) {
+    if (pre_.Adopt(text, nbytes, compute_->get())) return;
+    pre_.Drop();
+    LaunchCountScan(text, nbytes, pre_.cur, compute_->get());
   }
 
   /*!
@@ -727,46 +743,12 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
    *  take the exact path.  One blocking read-back (the chunk's sizes) before
    *  the fill, one for the maxima / flags after it.
    */
-  /*! \brief the tile pipeline's count + scan (LibSVM / LibFM C1 + C2, or CSV S1 + scan) */
-  void LaunchCountScan(const char* text, size_t nbytes, uint64_t* counts, uint32_t* flags,
-                       uint32_t* masks, ChunkMeta* dmeta, ChunkMeta* hm, hipStream_t s) {
-    if (tcfg_.format == TextFormat::kCSV) {
-      LaunchCsvTileCount(text, nbytes, tcfg_.label_column, tcfg_.weight_column, tcfg_.delimiter,
-                         counts, flags, masks, s);
-      LaunchTileScanRaw(counts, flags, TileCount(nbytes), dmeta, hm, s);
-    } else {
-      LaunchTileCountScan(text, nbytes, counts, flags, masks, dmeta, hm, s);
-    }
-  }
-
-  /*! \brief count + scan of this chunk into the current scratch set: adopt the
-   *  prelaunched set when it holds this chunk, else launch them now */
-  void CountScanCurrent(const char* text, size_t nbytes) {
-    if (pre_.valid && pre_.text == text && pre_.nbytes == nbytes) {
-      // queued behind the previous fill: take over that scratch set (its sizes
-      // are published, or about to be, in hmap_next_)
-      tcounts_.swap(tcounts_next_);
-      tflags_.swap(tflags_next_);
-      tmasks_.swap(tmasks_next_);
-      meta_.swap(meta_next_);
-      hmap_.swap(hmap_next_);
-      pre_.valid = false;
-      // the fill reads the tile prefix the other stream wrote
-      DMLC_HIP_CHECK(hipStreamWaitEvent(compute_->get(), pre_done_->get(), 0));
-      return;
-    }
-    DropPrelaunch();
-    LaunchCountScan(text, nbytes, tcounts_.get<uint64_t>(), tflags_.get<uint32_t>(),
-                    tmasks_.get<uint32_t>(), meta_.get<ChunkMeta>(), hmap_.get<ChunkMeta>(),
-                    compute_->get());
-  }
-
   bool FastParse(const char* text, size_t nbytes, DeviceCSR<IndexType>* out, size_t row_base,
                  size_t nnz_base, ChunkPlan* plan) {
     hipStream_t s = compute_->get();
     CountScanCurrent(text, nbytes);
-    ChunkMeta* dmeta = meta_.get<ChunkMeta>();
-    ChunkMeta* hm = hmap_.get<ChunkMeta>();
+    ChunkMeta* dmeta = pre_.cur.dmeta();
+    ChunkMeta* hm = pre_.cur.hmeta();
     const ChunkMeta sizes = WaitMapped(hm);
     AfterFirstSync();
     if (sizes.flags & kFlagIrregular) return false;
@@ -783,8 +765,8 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
         // rows without a `qid:` token have qid 0; the fill writes the others
         DMLC_HIP_CHECK(hipMemsetAsync(tgt.qid + row_base, 0, plan->nrows * sizeof(uint64_t), s));
       }
-      LaunchTileFill<IndexType>(text, nbytes, tcfg_.format, tcounts_.get<uint64_t>(),
-                                tmasks_.get<uint32_t>(), tgt,
+      LaunchTileFill<IndexType>(text, nbytes, tcfg_.format, pre_.cur.counts.get<uint64_t>(),
+                                pre_.cur.masks.get<uint32_t>(), tgt,
                                 slots_.get<MetaPartial>(), dmeta, hm, s);
       PrelaunchCount();
       ChunkMeta m = WaitMapped(hm);
@@ -815,8 +797,8 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
     hipStream_t s = compute_->get();
     const size_t ntiles = TileCount(nbytes);
     CountScanCurrent(text, nbytes);
-    ChunkMeta* dmeta = meta_.get<ChunkMeta>();
-    ChunkMeta* hm = hmap_.get<ChunkMeta>();
+    ChunkMeta* dmeta = pre_.cur.dmeta();
+    ChunkMeta* hm = pre_.cur.hmeta();
     const ChunkMeta sizes = WaitMapped(hm);
     AfterFirstSync();
     if (sizes.flags & kFlagIrregular) return false;
@@ -826,8 +808,8 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
     const bool need_weight = tcfg_.weight_column >= 0;
     FillTarget<IndexType> tgt = PrepareOutput(out, row_base, nnz_base, *plan, need_weight, nbytes);
     LaunchCsvTileFill<IndexType>(text, nbytes, tcfg_.label_column, tcfg_.weight_column,
-                                 tcfg_.delimiter, tcounts_.get<uint64_t>(),
-                                 tmasks_.get<uint32_t>(), tgt,
+                                 tcfg_.delimiter, pre_.cur.counts.get<uint64_t>(),
+                                 pre_.cur.masks.get<uint32_t>(), tgt,
                                  slots_.get<MetaPartial>(), s);
     LaunchTileFinish(slots_.get<MetaPartial>(), ntiles, dmeta, hm, tgt.offset, row_base, nnz_base,
                      s);
@@ -840,28 +822,41 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
     return true;
   }
 
+  /*!
+   * \brief the exact kernels' index of a chunk: K1 line starts (lines_), K2
+   *  per-line row validity / entry counts and K3 their scan (info_); returns
+   *  the chunk's lines, rows, entries and K2's flags (two read-backs)
+   */
+  ChunkPlan ExactIndex(const char* text, size_t nbytes, bool first_sync_done) {
+    hipStream_t s = compute_->get();
+    ChunkMeta* dmeta = pre_.cur.dmeta();
+    ChunkPlan plan;
+    DMLC_HIP_CHECK(hipMemsetAsync(dmeta, 0, sizeof(ChunkMeta), s));
+    LaunchLineCount(text, nbytes, tiles_.get<uint64_t>(), dmeta, s);
+    plan.nlines = ReadBack<ChunkMeta>(dmeta).nlines;
+    if (!first_sync_done) AfterFirstSync();
+    EnsureLineBuffers(plan.nlines);
+    LaunchLineEmit(text, nbytes, tiles_.get<uint64_t>(), lines_.get<uint32_t>(), s);
+    LaunchTextCount(text, nbytes, lines_.get<uint32_t>(), plan.nlines, tcfg_,
+                    info_.get<uint64_t>(), slots_.get<MetaPartial>(), dmeta, s);
+    uint64_t* total = partials_.get<uint64_t>() + ScanPartials(plan.nlines) + 1;
+    LaunchScanU64(info_.get<uint64_t>(), plan.nlines, partials_.get<uint64_t>(), total, s);
+    LaunchMetaFromTotal(total, dmeta, s);
+    const ChunkMeta hm = ReadBack<ChunkMeta>(dmeta);
+    plan.nrows = hm.nrows;
+    plan.nnz = hm.nnz;
+    plan.flags = hm.flags;
+    return plan;
+  }
+
   /*! \brief exact wave-per-line parse (any input) */
   void ExactParse(const char* text, size_t nbytes, DeviceCSR<IndexType>* out, size_t row_base,
                   size_t nnz_base, ChunkPlan* plan, bool first_sync_done) {
     hipStream_t s = compute_->get();
-    ChunkMeta* dmeta = meta_.get<ChunkMeta>();
-    DMLC_HIP_CHECK(hipMemsetAsync(dmeta, 0, sizeof(ChunkMeta), s));
-    LaunchLineCount(text, nbytes, tiles_.get<uint64_t>(), dmeta, s);
-    plan->nlines = ReadBack<ChunkMeta>(dmeta).nlines;
-    if (!first_sync_done) AfterFirstSync();
-    EnsureLineBuffers(plan->nlines);
-    LaunchLineEmit(text, nbytes, tiles_.get<uint64_t>(), lines_.get<uint32_t>(), s);
-    LaunchTextCount(text, nbytes, lines_.get<uint32_t>(), plan->nlines, tcfg_,
-                    info_.get<uint64_t>(), slots_.get<MetaPartial>(), dmeta, s);
-    uint64_t* total = partials_.get<uint64_t>() + ScanPartials(plan->nlines) + 1;
-    LaunchScanU64(info_.get<uint64_t>(), plan->nlines, partials_.get<uint64_t>(), total, s);
-    LaunchMetaFromTotal(total, dmeta, s);
-    const ChunkMeta hm = ReadBack<ChunkMeta>(dmeta);
-    plan->nrows = hm.nrows;
-    plan->nnz = hm.nnz;
-    plan->flags = hm.flags;
+    ChunkMeta* dmeta = pre_.cur.dmeta();
+    *plan = ExactIndex(text, nbytes, first_sync_done);
     const bool csv = tcfg_.format == TextFormat::kCSV;
-    const bool need_weight = (hm.flags & kFlagWeight) || (csv && tcfg_.weight_column >= 0);
+    const bool need_weight = (plan->flags & kFlagWeight) || (csv && tcfg_.weight_column >= 0);
     FillTarget<IndexType> tgt = PrepareOutput(out, row_base, nnz_base, *plan, need_weight, nbytes);
     DMLC_HIP_CHECK(hipMemsetAsync(dmeta, 0, sizeof(ChunkMeta), s));
     LaunchTextFill<IndexType>(text, nbytes, lines_.get<uint32_t>(), plan->nlines, tcfg_,
@@ -904,7 +899,7 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
 
   /*!
    * \brief the next epoch's first merged chunk (replay_list_ from the start,
-   *  the first merge cap FillPipeline will use), counted now on count_stream_
+   *  the first merge cap FillPipeline will use), counted now on the count stream
    *  so the next pass's first fill does not wait for its count.  A next pass
    *  that starts otherwise drops it unused (CountScanCurrent matches text and
    *  size).
@@ -929,28 +924,12 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
   }
 
   void PrelaunchFor(const char* text, size_t nbytes) {
-    const size_t tiles = TileCount(nbytes);
-    tcounts_next_.Reserve(TileScratchWords(tiles) * sizeof(uint64_t));
-    tflags_next_.Reserve(TileScratchWords(tiles) * sizeof(uint32_t));
-    tmasks_next_.Reserve(TileMaskWords(tiles) * sizeof(uint32_t));
     // its own stream: count + scan (HBM- and VALU-light next to the fill)
-    // overlap the current fill instead of queueing behind it.  The set it
-    // writes was last used by the chunk before the current one, which is done.
-    LaunchCountScan(text, nbytes, tcounts_next_.get<uint64_t>(), tflags_next_.get<uint32_t>(),
-                    tmasks_next_.get<uint32_t>(), meta_next_.get<ChunkMeta>(),
-                    hmap_next_.get<ChunkMeta>(), count_stream_->get());
-    pre_done_->Record(count_stream_->get());
-    pre_.valid = true;
-    pre_.text = text;
-    pre_.nbytes = nbytes;
-  }
-
-  /*! \brief retire a prelaunched count nobody will adopt (its flag re-armed) */
-  void DropPrelaunch() {
-    if (!pre_.valid) return;
-    count_stream_->Synchronize();
-    static_cast<ChunkMeta*>(hmap_next_.get())->pad = 0;
-    pre_.valid = false;
+    // overlap the current fill instead of queueing behind it
+    pre_.Launch(text, nbytes, TileCount(nbytes), /*with_masks=*/true,
+                [&](const TileScratchSet& set, hipStream_t s) {
+                  LaunchCountScan(text, nbytes, set, s);
+                });
   }
 
   /*! \brief the H2D of the current chunk is complete: recycle and keep PCIe busy */
@@ -959,7 +938,6 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
     FillPipeline();
   }
 
-  /*! \brief parse one chunk into out (append or replace); false at end */
   /*!
    * \brief pop the next device-resident chunk and run body(text, nbytes) on it
    *  (compute stream, after its H2D); false at the end.  Slot recycling and
@@ -1022,38 +1000,23 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
   OnePass OnePassParse(const char* text, size_t nbytes, DeviceCSR<IndexType>* out, size_t row_base,
                        size_t nnz_base, ChunkPlan* plan) {
     hipStream_t s = compute_->get();
-    DropPrelaunch();
-    ChunkMeta* dmeta = meta_.get<ChunkMeta>();
-    ChunkMeta* hm = hmap_.get<ChunkMeta>();
+    pre_.Drop();
+    ChunkMeta* dmeta = pre_.cur.dmeta();
+    ChunkMeta* hm = pre_.cur.hmeta();
     const bool libfm = tcfg_.format == TextFormat::kLibFM;
     const size_t tiles = TileCount(nbytes);
     fstatus_.Reserve(tiles * sizeof(uint64_t));  // zeroed by the launcher, per launch
-    if (hticket_.bytes() == 0) {
-      hticket_.Reserve(sizeof(unsigned long long));
-      DMLC_HIP_CHECK(hipMemsetAsync(hticket_.get(), 0, hticket_.bytes(), s));
-      hticket0_ = 0;
-    }
+    tickets_.Ensure(s);
     bool first_wait = true;
     for (;;) {
-      FillTarget<IndexType> tgt;
-      tgt.offset = out->offset();
-      tgt.label = out->label();
-      tgt.weight = out->weight_capacity() >= out->row_capacity() && out->row_capacity() != 0
-                       ? out->weight()
-                       : nullptr;
-      tgt.qid = nullptr;  // qid chunks take the counted path
-      tgt.field = libfm ? out->field() : nullptr;
-      tgt.index = out->index();
-      tgt.value = out->value();
-      tgt.row_base = row_base;
-      tgt.nnz_base = nnz_base;
-      // every row / entry the capacity holds (the row pointer has one slot more)
-      tgt.row_limit = out->row_capacity();
-      tgt.nnz_limit = out->nnz_capacity();
+      // every row / entry the capacity holds (the row pointer has one slot
+      // more); no qid column: qid chunks take the counted path
+      FillTarget<IndexType> tgt = MakeFillTarget(out, row_base, nnz_base, out->row_capacity(),
+                                                 out->nnz_capacity(), /*with_qid=*/false);
       if (libfm && tgt.field == nullptr) tgt.nnz_limit = 0;
-      const FillOnePass op{fstatus_.get<uint64_t>(), hticket_.get<unsigned long long>(), hticket0_};
-      hticket0_ += LaunchTileFill<IndexType>(text, nbytes, tcfg_.format, nullptr, nullptr, tgt,
-                                             slots_.get<MetaPartial>(), dmeta, hm, s, &op);
+      const FillOnePass op{tickets_.For(fstatus_.get<uint64_t>())};
+      tickets_.Advance(LaunchTileFill<IndexType>(text, nbytes, tcfg_.format, nullptr, nullptr, tgt,
+                                                 slots_.get<MetaPartial>(), dmeta, hm, s, &op));
       ChunkMeta m = WaitMapped(hm);
       if (first_wait) {
         AfterFirstSync();
@@ -1092,6 +1055,7 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
     }
   }
 
+  /*! \brief parse one chunk into out (append or replace); false at end */
   bool ProcessOne(DeviceCSR<IndexType>* out, bool append) {
     const size_t row_base = append ? out->rows_ : 0;
     const size_t nnz_base = append ? out->nnz_ : 0;
@@ -1140,16 +1104,6 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
     out->dim = dim;
     out->fp8 = fp8;
     out->rows = 0;
-    // the first chunk sizes the batch for the whole partition from its density
-    // (no doubling copies of a multi-GB batch); a reused batch usually fits already
-    auto reserve = [&](size_t chunk_rows, size_t nbytes) {
-      if (out->rows == 0) {
-        const double f = static_cast<double>(PartitionBytes()) / std::max<size_t>(nbytes, 1);
-        out->Reserve(static_cast<size_t>(chunk_rows * f * 1.02) + 1, compute_->get());
-      }
-      out->Reserve(out->rows + chunk_rows, compute_->get());
-    };
-    hipStream_t s = compute_->get();
     merge_replay_ = true;  // resident text: parse adjacent cached chunks together
     struct Unmerge {
       bool* f;
@@ -1166,107 +1120,121 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
     // 1.91 ms per 1.49 GB pass with the whole pass in one chunk; below 2 GiB:
     // an irregular chunk falls back to the exact kernels' 32-bit offsets, as
     // DeviceParserConfig::Update checks for replay_chunk_bytes)
-    const bool one_pass =
-        cfg_.hash_one_pass && cfg_.fast_path && dim % 16 == 0 && replay_ && out->row_cap != 0;
-    if (replay_ && out->row_cap != 0 && cfg_.fast_path && dim % 16 == 0) {
+    const bool tile = cfg_.fast_path && dim % 16 == 0;  // else the exact kernels alone
+    const bool one_pass = cfg_.hash_one_pass && tile && replay_ && out->row_cap != 0;
+    if (replay_ && out->row_cap != 0 && tile) {
       merge_limit_ = std::min(2 * cfg_.replay_chunk_bytes, (size_t(1) << 31) - (size_t(64) << 20));
       if (merge_cap_ == 0) merge_cap_ = merge_limit_;
     }
     while (WithNextChunk([&](const char* text, size_t nbytes) {
-      ChunkMeta* dmeta = meta_.get<ChunkMeta>();
+      bool done = false;
       if (one_pass && nbytes != 0 && out->row_cap != 0) {
-        DropPrelaunch();
-        ChunkMeta* hm = hmap_.get<ChunkMeta>();
-        const size_t tiles = TileCount(nbytes);
-        if (hstatus_.bytes() < tiles * sizeof(uint64_t)) {
-          hstatus_.Reserve(tiles * sizeof(uint64_t));
-          DMLC_HIP_CHECK(hipMemsetAsync(hstatus_.get(), 0, hstatus_.bytes(), s));
-        }
-        if (hticket_.bytes() == 0) {
-          hticket_.Reserve(sizeof(unsigned long long));
-          DMLC_HIP_CHECK(hipMemsetAsync(hticket_.get(), 0, hticket_.bytes(), s));
-          hticket0_ = 0;
-        }
-        for (;;) {
-          if (++htag_ >= (1u << 30)) {  // tags wrapped: old words could match again
-            htag_ = 1;
-            DMLC_HIP_CHECK(hipMemsetAsync(hstatus_.get(), 0, hstatus_.bytes(), s));
-          }
-          const HashOnePass op{hstatus_.get<uint64_t>(), hticket_.get<unsigned long long>(),
-                               hticket0_, htag_, out->row_cap};
-          hticket0_ += LaunchTileHashed<IndexType>(
-              text, nbytes, tcfg_.format, nullptr, nullptr, out->rows, 0, dim, scale, seed, fp8,
-              out->x->get(), out->label->get<float>(), slots_.get<MetaPartial>(), dmeta, hm, s, &op);
-          const ChunkMeta m = WaitMapped(hm);
-          AfterFirstSync();
-          CHECK(!(m.flags & kFlagNegIndex)) << "negative feature index in " << cfg_.format
-                                            << " input";
-          if (m.flags & kFlagIrregular) break;  // the exact kernels, below
-          if (m.flags & kFlagOverflow) {
-            // more rows than the batch holds: grow it, write the chunk again
-            reserve(m.nrows, nbytes);
-            continue;
-          }
-          out->rows += m.nrows;
-          stats_.rows += m.nrows;
-          stats_.one_pass_chunks += 1;
-          return;
-        }
-        stats_.exact_chunks += 1;
-      } else if (cfg_.fast_path && dim % 16 == 0) {
-        // tile parser: C1 + C2 sizes, then the fused tile kernel builds the
-        // rows of the lines each workgroup owns
-        CountScanCurrent(text, nbytes);  // may adopt a prelaunched count + scan
-        dmeta = meta_.get<ChunkMeta>();
-        ChunkMeta* hm = hmap_.get<ChunkMeta>();
-        const ChunkMeta sizes = WaitMapped(hm);
-        AfterFirstSync();
-        if (!(sizes.flags & kFlagIrregular)) {
-          reserve(sizes.nrows, nbytes);
-          LaunchTileHashed<IndexType>(text, nbytes, tcfg_.format, tcounts_.get<uint64_t>(),
-                                      tmasks_.get<uint32_t>(), out->rows, sizes.nlines, dim, scale,
-                                      seed, fp8, out->x->get(),
-                                      out->label->get<float>(), slots_.get<MetaPartial>(), dmeta,
-                                      hm, s);
-          PrelaunchCount();
-          const ChunkMeta m = WaitMapped(hm);
-          CHECK(!(m.flags & kFlagNegIndex)) << "negative feature index in " << cfg_.format
-                                            << " input";
-          if (!(m.flags & kFlagIrregular)) {
-            out->rows += sizes.nrows;
-            stats_.rows += sizes.nrows;
-            return;
-          }
-        }
-        stats_.exact_chunks += 1;
+        done = HashedOnePass(text, nbytes, out, scale, seed);
+      } else if (tile) {
+        done = HashedCounted(text, nbytes, out, scale, seed);
       }
-      // K1 line index, K2 row validity + K3 scan (as the exact CSR path), then
-      // the fused per-line hash kernel writes rows straight into the batch
-      DMLC_HIP_CHECK(hipMemsetAsync(dmeta, 0, sizeof(ChunkMeta), s));
-      LaunchLineCount(text, nbytes, tiles_.get<uint64_t>(), dmeta, s);
-      const size_t nlines = ReadBack<ChunkMeta>(dmeta).nlines;
-      if (!(cfg_.fast_path && dim % 16 == 0)) AfterFirstSync();
-      EnsureLineBuffers(nlines);
-      LaunchLineEmit(text, nbytes, tiles_.get<uint64_t>(), lines_.get<uint32_t>(), s);
-      LaunchTextCount(text, nbytes, lines_.get<uint32_t>(), nlines, tcfg_, info_.get<uint64_t>(),
-                      slots_.get<MetaPartial>(), dmeta, s);
-      uint64_t* total = partials_.get<uint64_t>() + ScanPartials(nlines) + 1;
-      LaunchScanU64(info_.get<uint64_t>(), nlines, partials_.get<uint64_t>(), total, s);
-      LaunchMetaFromTotal(total, dmeta, s);
-      const size_t nrows = ReadBack<ChunkMeta>(dmeta).nrows;
-      reserve(nrows, nbytes);
-      DMLC_HIP_CHECK(hipMemsetAsync(dmeta, 0, sizeof(ChunkMeta), s));
-      LaunchTextHashed<IndexType>(text, nbytes, lines_.get<uint32_t>(), nlines, tcfg_.format,
-                                  info_.get<uint64_t>(), out->rows, dim, scale, seed, fp8,
-                                  out->x->get(), out->label->get<float>(), slots_.get<MetaPartial>(),
-                                  dmeta, s);
-      const ChunkMeta m = ReadBack<ChunkMeta>(dmeta);
-      CHECK(!(m.flags & kFlagNegIndex)) << "negative feature index in " << cfg_.format << " input";
-      out->rows += nrows;
-      stats_.rows += nrows;
+      if (tile && !done) stats_.exact_chunks += 1;
+      if (!done) HashedExact(text, nbytes, out, scale, seed, /*first_sync_done=*/tile);
     })) {
     }
     compute_->Synchronize();
+  }
+
+  /*! \brief room for chunk_rows more rows.  The first chunk sizes the batch for
+   *  the whole partition from its density (no doubling copies of a multi-GB
+   *  batch); a reused batch usually fits already */
+  void ReserveHashed(DeviceHashedBatch* out, size_t chunk_rows, size_t nbytes) {
+    if (out->rows == 0) {
+      const double f = static_cast<double>(PartitionBytes()) / std::max<size_t>(nbytes, 1);
+      out->Reserve(static_cast<size_t>(chunk_rows * f * 1.02) + 1, compute_->get());
+    }
+    out->Reserve(out->rows + chunk_rows, compute_->get());
+  }
+
+  void CheckHashed(const ChunkMeta& m) {
+    CHECK(!(m.flags & kFlagNegIndex)) << "negative feature index in " << cfg_.format << " input";
+  }
+
+  /*! \brief one pass over a resident chunk into a batch that has capacity
+   *  (k_tile_hash look-back, no C1 / C2); false: irregular, the exact kernels */
+  bool HashedOnePass(const char* text, size_t nbytes, DeviceHashedBatch* out, float scale,
+                     uint32_t seed) {
+    hipStream_t s = compute_->get();
+    pre_.Drop();
+    ChunkMeta* dmeta = pre_.cur.dmeta();
+    ChunkMeta* hm = pre_.cur.hmeta();
+    const size_t tiles = TileCount(nbytes);
+    if (hstatus_.bytes() < tiles * sizeof(uint64_t)) {
+      hstatus_.Reserve(tiles * sizeof(uint64_t));
+      DMLC_HIP_CHECK(hipMemsetAsync(hstatus_.get(), 0, hstatus_.bytes(), s));
+    }
+    tickets_.Ensure(s);
+    for (;;) {
+      if (++htag_ >= (1u << 30)) {  // tags wrapped: old words could match again
+        htag_ = 1;
+        DMLC_HIP_CHECK(hipMemsetAsync(hstatus_.get(), 0, hstatus_.bytes(), s));
+      }
+      const HashOnePass op{tickets_.For(hstatus_.get<uint64_t>()), htag_, out->row_cap};
+      tickets_.Advance(LaunchTileHashed<IndexType>(
+          text, nbytes, tcfg_.format, nullptr, nullptr, out->rows, 0, out->dim, scale, seed,
+          out->fp8, out->x->get(), out->label->get<float>(), slots_.get<MetaPartial>(), dmeta, hm,
+          s, &op));
+      const ChunkMeta m = WaitMapped(hm);
+      AfterFirstSync();
+      CheckHashed(m);
+      if (m.flags & kFlagIrregular) return false;
+      if (m.flags & kFlagOverflow) {
+        // more rows than the batch holds: grow it, write the chunk again
+        ReserveHashed(out, m.nrows, nbytes);
+        continue;
+      }
+      out->rows += m.nrows;
+      stats_.rows += m.nrows;
+      stats_.one_pass_chunks += 1;
+      return true;
+    }
+  }
+
+  /*! \brief tile parser: C1 + C2 sizes, then the fused tile kernel builds the
+   *  rows of the lines each workgroup owns; false: irregular, the exact kernels */
+  bool HashedCounted(const char* text, size_t nbytes, DeviceHashedBatch* out, float scale,
+                     uint32_t seed) {
+    hipStream_t s = compute_->get();
+    CountScanCurrent(text, nbytes);  // may adopt a prelaunched count + scan
+    ChunkMeta* hm = pre_.cur.hmeta();
+    const ChunkMeta sizes = WaitMapped(hm);
+    AfterFirstSync();
+    if (sizes.flags & kFlagIrregular) return false;
+    ReserveHashed(out, sizes.nrows, nbytes);
+    LaunchTileHashed<IndexType>(text, nbytes, tcfg_.format, pre_.cur.counts.get<uint64_t>(),
+                                pre_.cur.masks.get<uint32_t>(), out->rows, sizes.nlines, out->dim,
+                                scale, seed, out->fp8, out->x->get(), out->label->get<float>(),
+                                slots_.get<MetaPartial>(), pre_.cur.dmeta(), hm, s);
+    PrelaunchCount();
+    const ChunkMeta m = WaitMapped(hm);
+    CheckHashed(m);
+    if (m.flags & kFlagIrregular) return false;
+    out->rows += sizes.nrows;
+    stats_.rows += sizes.nrows;
+    return true;
+  }
+
+  /*! \brief K1 line index, K2 row validity + K3 scan (as the exact CSR path),
+   *  then the fused per-line hash kernel writes rows straight into the batch */
+  void HashedExact(const char* text, size_t nbytes, DeviceHashedBatch* out, float scale,
+                   uint32_t seed, bool first_sync_done) {
+    hipStream_t s = compute_->get();
+    ChunkMeta* dmeta = pre_.cur.dmeta();
+    const ChunkPlan plan = ExactIndex(text, nbytes, first_sync_done);
+    ReserveHashed(out, plan.nrows, nbytes);
+    DMLC_HIP_CHECK(hipMemsetAsync(dmeta, 0, sizeof(ChunkMeta), s));
+    LaunchTextHashed<IndexType>(text, nbytes, lines_.get<uint32_t>(), plan.nlines, tcfg_.format,
+                                info_.get<uint64_t>(), out->rows, out->dim, scale, seed, out->fp8,
+                                out->x->get(), out->label->get<float>(), slots_.get<MetaPartial>(),
+                                dmeta, s);
+    CheckHashed(ReadBack<ChunkMeta>(dmeta));
+    out->rows += plan.nrows;
+    stats_.rows += plan.nrows;
   }
 
   /*! \brief publish the accumulated max / flags of this epoch */
@@ -1291,24 +1259,14 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
   std::unique_ptr<Stream> compute_, copy_;
   std::vector<std::unique_ptr<DeviceBuffer>> dtext_;
   std::vector<std::unique_ptr<Event>> copied_, parsed_;
-  DeviceBuffer tiles_, lines_, info_, partials_, meta_;
-  /*! \brief tile parser scratch: per-tile counts (scanned in place) and flags */
-  DeviceBuffer tcounts_, tflags_, tmasks_;
-  // the prelaunched next chunk's C1 + C2 scratch (hbm_cache ParseAll only)
-  DeviceBuffer tcounts_next_, tflags_next_, tmasks_next_, meta_next_;
-  PinnedBuffer hmap_next_;
-  std::unique_ptr<Stream> count_stream_;  // prelaunched counts (hbm_cache only)
-  std::unique_ptr<Event> pre_done_;
-  struct Prelaunch {
-    bool valid{false};
-    const char* text{nullptr};
-    size_t nbytes{0};
-  } pre_;
+  DeviceBuffer tiles_, lines_, info_, partials_;
+  /*! \brief tile parser scratch (pre_.cur: counts, flags, masks, the device
+   *  ChunkMeta and the mapped pinned one the tile kernels write directly) and,
+   *  with hbm_cache, the prelaunched next chunk's C1 + C2 set and stream */
+  CountPrelaunch pre_;
   /*! \brief per-workgroup reduction slots (MetaPartial) */
   DeviceBuffer slots_;
   PinnedBuffer hmeta_;
-  /*! \brief mapped pinned ChunkMeta the tile kernels write directly */
-  PinnedBuffer hmap_;
   ThreadedIter<HostSlot> iter_;
   std::unique_ptr<ZeroCopySource> zc_;
   std::deque<Inflight> inflight_;
@@ -1318,14 +1276,15 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
   /*! \brief merged replay chunk cap of the pass (0: the next is the first) */
   size_t merge_cap_{0};
   size_t merge_limit_{0};  // merged replay chunk limit (0: replay_chunk_bytes)
-  // one-pass hashed batches: look-back words, workgroup tickets, launch tag
-  DeviceBuffer hstatus_, hticket_;
-  // one-pass CSR fill: look-back words (zeroed per launch; tickets shared)
+  // one-pass hashed batches: look-back words and their launch tag
+  DeviceBuffer hstatus_;
+  uint32_t htag_{0};
+  // one-pass CSR fill: look-back words (zeroed per launch)
   DeviceBuffer fstatus_;
+  /*! \brief workgroup tickets of both one-pass kernels */
+  OnePassTickets tickets_;
   /*! \brief qid data met: resident chunks take the counted tile path */
   bool one_pass_off_{false};
-  unsigned long long hticket0_{0};
-  uint32_t htag_{0};
   std::vector<CachedChunk> cached_;
   bool caching_{false}, cache_complete_{false}, replay_{false}, merge_replay_{false};
   HostSlot* cur_slot_{nullptr};

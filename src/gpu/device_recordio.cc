@@ -28,7 +28,6 @@
 #include <dmlc/timer.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <deque>
@@ -40,6 +39,7 @@
 #include "../io/uri_spec.h"
 #include "./host_wait.h"
 #include "./kernels.h"
+#include "./tile_pipeline.h"
 #include "./zero_copy_source.h"
 
 namespace dmlc {
@@ -125,14 +125,9 @@ class DeviceRecordIOImpl : public DeviceRecordIOReader {
     io::URI path(uri.c_str());
     io::FileSystem* fs = io::FileSystem::GetInstance(path);
     for (int d = 0; d < cfg_.device_slots; ++d) slots_.emplace_back(new DevSlot());
-    hmap_.Reserve(sizeof(ChunkMeta), /*mapped=*/true);
-    std::memset(hmap_.get(), 0, sizeof(ChunkMeta));
-    meta_.Reserve(sizeof(ChunkMeta));
-    // second R1 + scan scratch set: the next replayed piece's count runs on
-    // count_ while the current piece's fill runs (PrelaunchCount)
-    hmap_next_.Reserve(sizeof(ChunkMeta), /*mapped=*/true);
-    std::memset(hmap_next_.get(), 0, sizeof(ChunkMeta));
-    meta_next_.Reserve(sizeof(ChunkMeta));
+    // with a second R1 + scan scratch set: the next replayed piece's count runs
+    // on its own stream while the current piece's fill runs (PrelaunchCount)
+    pre_.Init(sizeof(ChunkMeta), /*with_next=*/true);
     if (!cfg_.index_uri.empty()) {
       indexed_.reset(new io::IndexedRecordIOSplitter(fs, uri.c_str(), cfg_.index_uri.c_str(), part,
                                                      nparts, 1, cfg_.shuffle, cfg_.seed));
@@ -156,7 +151,7 @@ class DeviceRecordIOImpl : public DeviceRecordIOReader {
   ~DeviceRecordIOImpl() override {
     (void)hipStreamSynchronize(copy_.get());
     (void)hipStreamSynchronize(compute_.get());
-    (void)hipStreamSynchronize(count_.get());
+    (void)hipStreamSynchronize(pre_.stream->get());
     for (auto& p : ready_) {
       if (p.host != nullptr) iter_.Recycle(&p.host);
     }
@@ -418,7 +413,7 @@ class DeviceRecordIOImpl : public DeviceRecordIOReader {
   void Drain(bool keep_prelaunch = false) {
     copy_.Synchronize();
     compute_.Synchronize();
-    if (!keep_prelaunch) DropPrelaunch();
+    if (!keep_prelaunch) pre_.Drop();
     for (auto& p : ready_) {
       if (p.host != nullptr) iter_.Recycle(&p.host);
     }
@@ -429,16 +424,10 @@ class DeviceRecordIOImpl : public DeviceRecordIOReader {
   // ------------------------------------------------------------ decode
   ChunkMeta WaitMeta() {
     const double t0 = GetTime();
-    ChunkMeta* hm = hmap_.get<ChunkMeta>();
-    volatile unsigned* flag = &hm->pad;
-    if (!WaitHostFlag(flag, cfg_.wait_spin_us, 0.05, &waits_)) {
+    const ChunkMeta m = TakePublished(pre_.cur.hmeta(), cfg_.wait_spin_us, 0.05, &waits_, [this] {
       compute_.Synchronize();
-      count_.Synchronize();
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    ChunkMeta m;
-    std::memcpy(&m, const_cast<const ChunkMeta*>(hm), sizeof(m));
-    *flag = 0;  // re-armed before the next publishing kernel
+      pre_.stream->Synchronize();
+    });
     stats_.wait_gpu_sec += GetTime() - t0;
     return m;
   }
@@ -456,28 +445,25 @@ class DeviceRecordIOImpl : public DeviceRecordIOReader {
    */
   void DecodeOnePass(const Piece& p) {
     hipStream_t st = compute_.get();
-    DropPrelaunch();
+    pre_.Drop();
     const size_t nwords = p.bytes / 4;
     const size_t tiles = RecordIOTiles(nwords);
     partials_.Reserve(TileScratchSlots(tiles) * sizeof(MetaPartial));
     status_.Reserve(tiles * sizeof(uint64_t));
-    if (ticket_.bytes() == 0) {
-      ticket_.Reserve(sizeof(unsigned long long));
-      DMLC_HIP_CHECK(hipMemsetAsync(ticket_.get(), 0, ticket_.bytes(), st));
-      ticket0_ = 0;
-    }
-    ChunkMeta* dmeta = meta_.get<ChunkMeta>();
-    ChunkMeta* hm = hmap_.get<ChunkMeta>();
+    tickets_.Ensure(st);
+    ChunkMeta* dmeta = pre_.cur.dmeta();
+    ChunkMeta* hm = pre_.cur.hmeta();
     ChunkMeta done;
     for (;;) {
       // into the capacity the resident output has (an earlier epoch sized it)
       uint64_t* off = res_off_.get<uint64_t>();
       uint8_t* dat = res_data_.get<uint8_t>();
       const size_t rec_cap = res_off_.bytes() / sizeof(uint64_t);
-      const RecordIOOnePass op{status_.get<uint64_t>(), ticket_.get<unsigned long long>(),
-                               ticket0_, dmeta, rec_cap > 0 ? rec_cap - 1 : 0, res_data_.bytes()};
-      ticket0_ += LaunchRecordIOTileFill(p.words, nwords, nullptr, off, resident_rows_, dat,
-                                         resident_bytes_, partials_.get<MetaPartial>(), st, &op);
+      const RecordIOOnePass op{tickets_.For(status_.get<uint64_t>()), dmeta,
+                               rec_cap > 0 ? rec_cap - 1 : 0, res_data_.bytes()};
+      tickets_.Advance(LaunchRecordIOTileFill(p.words, nwords, nullptr, off, resident_rows_, dat,
+                                              resident_bytes_, partials_.get<MetaPartial>(), st,
+                                              &op));
       LaunchTileFinish(partials_.get<MetaPartial>(), tiles, dmeta, hm, off, resident_rows_,
                        resident_bytes_, st);
       done = WaitMeta();
@@ -508,26 +494,15 @@ class DeviceRecordIOImpl : public DeviceRecordIOReader {
     if (p.slot >= 0) DMLC_HIP_CHECK(hipStreamWaitEvent(st, slots_[p.slot]->copied.get(), 0));
     const size_t nwords = p.bytes / 4;
     const size_t tiles = RecordIOTiles(nwords);
-    if (pre_.valid && pre_.words == p.words && pre_.bytes == p.bytes) {
-      // R1 + scan of this piece ran on count_ beside the previous fill: adopt
-      // that scratch set; the fill waits for the scan that wrote its prefix
-      tcounts_.swap(tcounts_next_);
-      tflags_.swap(tflags_next_);
-      meta_.swap(meta_next_);
-      hmap_.swap(hmap_next_);
-      pre_.valid = false;
-      DMLC_HIP_CHECK(hipStreamWaitEvent(st, pre_done_.get(), 0));
-    } else {
-      DropPrelaunch();
-      tcounts_.Reserve(TileScratchWords(tiles) * sizeof(uint64_t));
-      tflags_.Reserve(TileScratchWords(tiles) * sizeof(uint32_t));
-      LaunchCount(p.words, nwords, tcounts_.get<uint64_t>(), tflags_.get<uint32_t>(), st);
-      LaunchTileScanRaw(tcounts_.get<uint64_t>(), tflags_.get<uint32_t>(), tiles,
-                        meta_.get<ChunkMeta>(), hmap_.get<ChunkMeta>(), st);
+    // adopt the R1 + scan of this piece if it ran beside the previous fill
+    if (!pre_.Adopt(p.words, p.bytes, st)) {
+      pre_.Drop();
+      pre_.cur.Reserve(tiles, /*with_masks=*/false);
+      LaunchCountScan(p.words, nwords, pre_.cur, st);
     }
     partials_.Reserve(TileScratchSlots(tiles) * sizeof(MetaPartial));
-    ChunkMeta* dmeta = meta_.get<ChunkMeta>();
-    ChunkMeta* hm = hmap_.get<ChunkMeta>();
+    ChunkMeta* dmeta = pre_.cur.dmeta();
+    ChunkMeta* hm = pre_.cur.hmeta();
     const ChunkMeta sizes = WaitMeta();
     // the copy of this piece is complete: its pinned slot goes back to the reader
     if (p.host != nullptr) iter_.Recycle(&p.host);
@@ -553,7 +528,7 @@ class DeviceRecordIOImpl : public DeviceRecordIOReader {
     const RecordIOCaps caps{dmeta,
                             (resident ? res_off_.bytes() : out_off_.bytes()) / sizeof(uint64_t) - 1,
                             resident ? res_data_.bytes() : out_data_.bytes()};
-    LaunchRecordIOTileFill(p.words, nwords, tcounts_.get<uint64_t>(), off, rec_base, dat, byte_base,
+    LaunchRecordIOTileFill(p.words, nwords, pre_.cur.counts.get<uint64_t>(), off, rec_base, dat, byte_base,
                            partials_.get<MetaPartial>(), st, nullptr, &caps);
     LaunchTileFinish(partials_.get<MetaPartial>(), tiles, dmeta, hm, off, rec_base, byte_base, st);
     if (resident) PrelaunchCount();
@@ -577,7 +552,7 @@ class DeviceRecordIOImpl : public DeviceRecordIOReader {
 
   /*!
    * \brief ReadAll over the HBM cache: start the next replayed piece's R1 +
-   *  scan on count_ (second scratch set) so it overlaps the current fill
+   *  scan on the count stream (second scratch set) so it overlaps the current fill
    *  instead of following the host's turnaround; the set it writes was last
    *  used by the piece before the current one, which is complete.
    */
@@ -597,7 +572,7 @@ class DeviceRecordIOImpl : public DeviceRecordIOReader {
   /*!
    * \brief at the end of a ReadAll over the HBM cache: the next epoch's
    *  first piece (the same merge from the first cached chunk) is counted
-   *  now, on count_, so the next ReadAll's first fill does not wait for its
+   *  now, on the count stream, so the next ReadAll's first fill does not wait for its
    *  count.  A next pass that starts with another piece (Next() batches)
    *  drops it unused.
    */
@@ -615,17 +590,18 @@ class DeviceRecordIOImpl : public DeviceRecordIOReader {
 
   void PrelaunchFor(const uint32_t* words, size_t bytes) {
     const size_t nwords = bytes / 4;
-    const size_t tiles = RecordIOTiles(nwords);
-    tcounts_next_.Reserve(TileScratchWords(tiles) * sizeof(uint64_t));
-    tflags_next_.Reserve(TileScratchWords(tiles) * sizeof(uint32_t));
-    LaunchCount(words, nwords, tcounts_next_.get<uint64_t>(), tflags_next_.get<uint32_t>(),
-                count_.get());
-    LaunchTileScanRaw(tcounts_next_.get<uint64_t>(), tflags_next_.get<uint32_t>(), tiles,
-                      meta_next_.get<ChunkMeta>(), hmap_next_.get<ChunkMeta>(), count_.get());
-    pre_done_.Record(count_.get());
-    pre_.valid = true;
-    pre_.words = words;
-    pre_.bytes = bytes;
+    pre_.Launch(words, bytes, RecordIOTiles(nwords), /*with_masks=*/false,
+                [&](const TileScratchSet& set, hipStream_t st) {
+                  LaunchCountScan(words, nwords, set, st);
+                });
+  }
+
+  /*! \brief R1 (or R1c) + scan of a piece into `set`, its sizes published to set.hmap */
+  void LaunchCountScan(const uint32_t* words, size_t nwords, const TileScratchSet& set,
+                       hipStream_t st) {
+    LaunchCount(words, nwords, set.counts.get<uint64_t>(), set.flags.get<uint32_t>(), st);
+    LaunchTileScanRaw(set.counts.get<uint64_t>(), set.flags.get<uint32_t>(), RecordIOTiles(nwords),
+                      set.dmeta(), set.hmeta(), st);
   }
 
   /*!
@@ -647,14 +623,6 @@ class DeviceRecordIOImpl : public DeviceRecordIOReader {
     }
   }
 
-  /*! \brief retire a prelaunched count nobody adopts (its flag re-armed) */
-  void DropPrelaunch() {
-    if (!pre_.valid) return;
-    count_.Synchronize();
-    hmap_next_.get<ChunkMeta>()->pad = 0;
-    pre_.valid = false;
-  }
-
   void GrowResident(size_t nrec, size_t bytes) {
     const size_t need_off = (resident_rows_ + nrec + 1) * sizeof(uint64_t);
     if (need_off > res_off_.bytes()) {
@@ -671,8 +639,7 @@ class DeviceRecordIOImpl : public DeviceRecordIOReader {
   std::unique_ptr<io::IndexedRecordIOSplitter> indexed_;
   std::unique_ptr<ZeroCopySource> zc_;
   ThreadedIter<HostSlot> iter_;
-  Stream copy_, compute_, count_;
-  Event pre_done_;
+  Stream copy_, compute_;
   std::vector<std::unique_ptr<DevSlot>> slots_;
   std::deque<Piece> ready_;
   int next_slot_{0};
@@ -687,21 +654,14 @@ class DeviceRecordIOImpl : public DeviceRecordIOReader {
   std::vector<uint64_t> tmp_src_, tmp_dst_;
   std::vector<uint32_t> tmp_len_;
   // decode scratch and outputs
-  DeviceBuffer tcounts_, tflags_, partials_, meta_;
-  PinnedBuffer hmap_;
-  // the prelaunched next piece's R1 + scan scratch (ReadAll over the HBM cache)
-  DeviceBuffer tcounts_next_, tflags_next_, meta_next_;
-  PinnedBuffer hmap_next_;
-  struct Prelaunch {
-    bool valid{false};
-    const uint32_t* words{nullptr};
-    size_t bytes{0};
-  } pre_;
+  DeviceBuffer partials_;
+  // R1 + scan scratch, and the prelaunched next piece's (ReadAll over the HBM cache)
+  CountPrelaunch pre_;
   HostWaitStats waits_;
   DeviceBuffer out_off_, out_data_, res_off_, res_data_;
   // one-pass replays: look-back words (zeroed per launch), workgroup tickets
-  DeviceBuffer status_, ticket_;
-  unsigned long long ticket0_{0};
+  DeviceBuffer status_;
+  OnePassTickets tickets_;
   size_t resident_rows_{0}, resident_bytes_{0};
   DeviceRecordBatch batch_, resident_;
   DeviceRecordIOStats stats_;

@@ -22,7 +22,9 @@
 #include <sys/prctl.h>
 #include <time.h>
 
+#include <atomic>
 #include <cstdint>
+#include <cstring>
 
 #include <dmlc/timer.h>
 
@@ -48,8 +50,10 @@ inline bool WaitHostFlag(const volatile unsigned* flag, double spin_us, double b
                          HostWaitStats* st) {
   const double t0 = GetTime();
   const double spin_end = t0 + spin_us * 1e-6;
+  // acquire (a plain load on x86): what the publisher wrote before is visible
+  auto raised = [flag] { return __atomic_load_n(flag, __ATOMIC_ACQUIRE) != 0; };
   for (uint32_t i = 0;; ++i) {
-    if (*flag != 0) {
+    if (raised()) {
       ++st->spun;
       return true;
     }
@@ -68,7 +72,7 @@ inline bool WaitHostFlag(const volatile unsigned* flag, double spin_us, double b
   } restore{old_slack};
   const struct timespec nap = {0, 5000};  // 5 us
   for (;;) {
-    if (*flag != 0) {
+    if (raised()) {
       ++st->slept;
       return true;
     }
@@ -78,6 +82,26 @@ inline bool WaitHostFlag(const volatile unsigned* flag, double spin_us, double b
     }
     nanosleep(&nap, nullptr);
   }
+}
+
+/*!
+ * \brief take the Meta a kernel publishes at *hm (mapped pinned memory; the
+ *  fields, a system fence, hm->pad raised last): poll the flag and, after
+ *  bound_s, call on_timeout() -- the caller synchronises the streams that can
+ *  publish there, so a kernel that never does (a fault) surfaces.  Returns a
+ *  copy and clears the flag: every published meta must be taken before the
+ *  next kernel that publishes to *hm is launched.
+ */
+template <typename Meta, typename OnTimeout>
+inline Meta TakePublished(Meta* hm, double spin_us, double bound_s, HostWaitStats* st,
+                          OnTimeout&& on_timeout) {
+  volatile unsigned* flag = &hm->pad;
+  if (!WaitHostFlag(flag, spin_us, bound_s, st)) on_timeout();
+  std::atomic_thread_fence(std::memory_order_acquire);
+  Meta v;
+  std::memcpy(&v, hm, sizeof(v));
+  __atomic_store_n(flag, 0u, __ATOMIC_RELAXED);
+  return v;
 }
 
 }  // namespace gpu

@@ -148,6 +148,13 @@ void LaunchCloseOffsets(uint64_t* offset, uint64_t row_end, uint64_t nnz_end, hi
 constexpr unsigned kFlagIrregular = 1024u;
 
 // --------------- LDS-staged tile parser (LibSVM/LibFM fast path) ---------------
+/*! \brief decoupled look-back state of a one-pass launch (tile, hash and
+ *  RecordIO fills): one status word per tile and the workgroup ticket counter */
+struct LookBack {
+  uint64_t* status;            // one word per tile of the chunk
+  unsigned long long* ticket;  // counter, zeroed once
+  unsigned long long ticket0;  // the counter's value before this launch
+};
 /*! \brief bytes of text per workgroup of the tile kernels */
 constexpr size_t kTileBytes = 8192;
 /*! \brief a weighted row met a FillTarget without a weight column (re-run with one) */
@@ -194,11 +201,7 @@ size_t TileMaskWords(size_t ntiles);
  *  path (LaunchTileCountScan first, qid column zeroed) writes -- run it so.
  *  Returns the workgroups launched: advance ticket0 by it.
  */
-struct FillOnePass {
-  uint64_t* status;            // >= TileCount(nbytes) words
-  unsigned long long* ticket;  // counter, zeroed once
-  unsigned long long ticket0;  // the counter's value before this launch
-};
+struct FillOnePass : LookBack {};  // status: >= TileCount(nbytes) words
 template <typename IndexType>
 size_t LaunchTileFill(const char* text, size_t nbytes, TextFormat format,
                       const uint64_t* tile_prefix, const uint32_t* tile_masks,
@@ -227,10 +230,7 @@ size_t LaunchTileFill(const char* text, size_t nbytes, TextFormat format,
  *  control bytes other than \t \n \r).  Returns the workgroups launched:
  *  advance ticket0 by it for the next launch on the same counter.
  */
-struct HashOnePass {
-  uint64_t* status;            // >= TileCount(nbytes) words, zeroed once at allocation
-  unsigned long long* ticket;  // counter, zeroed once
-  unsigned long long ticket0;  // the counter's value before this launch
+struct HashOnePass : LookBack {  // status: >= TileCount(nbytes) words, zeroed once at allocation
   uint32_t tag;                // distinct per launch on the same status array, 1..2^30-1
   uint64_t row_cap;            // rows of out / labels
 };
@@ -315,10 +315,7 @@ void LaunchRecordIOTileCount(const uint32_t* words, size_t nwords, uint64_t* til
  *  and run the chunk again.  Returns the workgroups launched (advance
  *  ticket0 by it).
  */
-struct RecordIOOnePass {
-  uint64_t* status;            // >= RecordIOTiles(nwords) words
-  unsigned long long* ticket;  // counter, zeroed once
-  unsigned long long ticket0;  // the counter's value before this launch
+struct RecordIOOnePass : LookBack {  // status: >= RecordIOTiles(nwords) words
   ChunkMeta* meta;
   uint64_t rec_cap;            // offset slots - 1
   uint64_t byte_cap;           // data bytes

@@ -1,7 +1,8 @@
 // L2 unit tests: the behaviours pinned by the reference's
 // test/unittest/unittest_{lockfree,thread_group,threaditer,
 // threaditer_exc_handling}.cc, plus the blocking queue and the
-// memory pool.  These are also the TSan targets (make tsan).
+// memory pool, and the host side of the GPU pipelines' published-meta wait
+// (src/gpu/host_wait.h).  These are also the TSan targets (make tsan).
 #include <dmlc/blockingconcurrentqueue.h>
 #include <dmlc/concurrency.h>
 #include <dmlc/concurrentqueue.h>
@@ -20,6 +21,7 @@
 #include <thread>
 #include <vector>
 
+#include "../../src/gpu/host_wait.h"
 #include "./testing.h"
 
 // ---------------------------------------------------------------- lock-free queue
@@ -364,4 +366,73 @@ TEST(Memory, ThreadlocalSharedPtr) {
   std::thread t([&] { distinct = dmlc::ThreadLocalStore<int>::Get() != main_ptr; });
   t.join();
   EXPECT_EQ(distinct.load(), 1);
+}
+
+// ---------------------------------------------------------------- published meta
+namespace {
+struct PlainMeta {
+  uint64_t a, b;
+  unsigned flags;
+  unsigned pad;
+};
+
+// what a publishing kernel does, from a second thread ~200 us later: the
+// fields, a release fence, the flag last
+PlainMeta TakeFromPublisher(PlainMeta* m, double spin_us, dmlc::gpu::HostWaitStats* st) {
+  std::thread publisher([m] {
+    std::this_thread::sleep_for(std::chrono::microseconds(200));
+    m->a = 11;
+    m->b = 22;
+    m->flags = 5;
+    std::atomic_thread_fence(std::memory_order_release);
+    __atomic_store_n(&m->pad, 1u, __ATOMIC_RELEASE);
+  });
+  const PlainMeta got = dmlc::gpu::TakePublished(m, spin_us, 5.0, st, [] {});
+  publisher.join();
+  return got;
+}
+}  // namespace
+
+TEST(HostWait, TakePublishedInSleepAndSpinPhase) {
+  dmlc::gpu::HostWaitStats st;
+  PlainMeta m{0, 0, 0, 0};
+  PlainMeta got = TakeFromPublisher(&m, /*spin_us=*/0, &st);  // no spin budget: found napping
+  EXPECT_EQ(got.a, 11U);
+  EXPECT_EQ(got.b, 22U);
+  EXPECT_EQ(got.flags, 5U);
+  EXPECT_EQ(got.pad, 1U);
+  EXPECT_EQ(m.pad, 0U);  // re-armed
+  EXPECT_EQ(st.slept, 1U);
+  EXPECT_EQ(st.spun, 0U);
+  m = PlainMeta{0, 0, 0, 0};
+  got = TakeFromPublisher(&m, /*spin_us=*/5e6, &st);  // found while spinning
+  EXPECT_EQ(got.a, 11U);
+  EXPECT_EQ(got.b, 22U);
+  EXPECT_EQ(got.flags, 5U);
+  EXPECT_EQ(m.pad, 0U);
+  EXPECT_EQ(st.spun, 1U);
+  EXPECT_EQ(st.slept, 1U);
+  EXPECT_EQ(st.timed_out, 0U);
+}
+
+TEST(HostWait, TakePublishedTimeoutCallsBackOnce) {
+  dmlc::gpu::HostWaitStats st;
+  PlainMeta m{0, 0, 0, 0};
+  int calls = 0;
+  // nobody raises the flag; the callback stands in for the stream
+  // synchronise after which the meta is there
+  const PlainMeta got = dmlc::gpu::TakePublished(&m, 50.0, /*bound_s=*/0.01, &st, [&] {
+    ++calls;
+    m.a = 7;
+    m.b = 8;
+    m.flags = 3;
+    m.pad = 1;
+  });
+  EXPECT_EQ(calls, 1);
+  EXPECT_EQ(got.a, 7U);
+  EXPECT_EQ(got.b, 8U);
+  EXPECT_EQ(got.flags, 3U);
+  EXPECT_EQ(m.pad, 0U);
+  EXPECT_EQ(st.timed_out, 1U);
+  EXPECT_EQ(st.spun + st.slept, 0U);
 }
