@@ -18,6 +18,12 @@ __all__ = ["Parser", "RowBlockIter", "GPUParser", "ShuffledGPUParser", "DeviceCS
            "write_page_cache"]
 
 write_synthetic = _dmlc.write_synthetic
+# packed H2D (src/gpu/text_pack.h): the host packer, its CPU reference unpack
+# and the device unpack kernel, for tests and measurements
+pack_text = _dmlc.pack_text
+pack_isa_supported = _dmlc.pack_isa_supported
+unpack_text_reference = _dmlc.unpack_text_reference
+unpack_text_device = _dmlc.unpack_text_device
 
 
 def _host_blocks_uri(uri: str) -> str:
@@ -85,7 +91,10 @@ class GPUParser:
     Parameters mirror ``dmlc::gpu::DeviceParserConfig``: ``format`` (libsvm |
     libfm | csv), ``chunk_mb``, ``pinned_slots``, ``device_slots``,
     ``read_threads``, ``device``, and CSV ``label_column`` / ``weight_column`` /
-    ``delimiter``.  URI ``?k=v`` arguments override them.
+    ``delimiter``.  ``packed_h2d`` ("auto" | 0 | 1): send chunks over PCIe as
+    4-bit codes packed by ``read_threads`` host threads and expand them on the
+    GPU (zero-copy source only; ``stats()`` reports ``packed_chunks``,
+    ``raw_chunks``, ``link_bytes``).  URI ``?k=v`` arguments override them.
     """
 
     def __init__(self, uri: str, part: int = 0, nparts: int = 1, format: str = "libsvm",  # noqa: A002

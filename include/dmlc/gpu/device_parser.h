@@ -80,6 +80,26 @@ struct DeviceParserConfig {
    */
   int zero_copy{-1};
   /*!
+   * \brief packed H2D (`?packed_h2d=`): with the zero-copy source, a pool of
+   *  read_threads threads encodes upcoming chunks as 4-bit codes
+   *  (src/gpu/text_pack.h) so half the bytes cross the PCIe link, and a kernel
+   *  expands them back to the same text in HBM.  A chunk that is not packed
+   *  by the time the link needs it goes raw.  -1 auto (on when the zero-copy
+   *  source is active, read_threads >= 2 and chunk_bytes >= 1 MiB), 0 off,
+   *  1 on for any chunk size.  Costs device_slots staging buffers of up to
+   *  3/4 chunk_bytes of HBM.
+   */
+  int packed_h2d{-1};
+  /*!
+   * \brief packed H2D, test and measurement hook (not a tuning knob): the
+   *  submitting thread waits for every chunk's pack
+   *  instead of sending a chunk the pool has not started raw (`?pack_wait=1`).
+   *  Only chunks the 3/4 size rule rejects go raw, so what is packed no longer
+   *  depends on timing: for tests and for measuring the pool's rate (stats
+   *  bytes / pack_sec); the link idles whenever the pool is the slower side.
+   */
+  bool pack_wait{false};
+  /*!
    * \brief zero-copy pinning: partitions up to zc_pin_budget bytes are
    *  registered whole, larger ones in sliding windows of zc_window_bytes (at
    *  most two pinned, the next prepared in the background)
@@ -126,8 +146,8 @@ struct DeviceParserConfig {
   int shuffle_seed{0};
   /*! \brief apply `?k=v` overrides (chunk_mb, pinned_slots, device_slots,
    *  read_threads, device, format, label_column, weight_column, delimiter,
-   *  fast_path, one_pass, prelaunch, zero_copy, zc_pin_budget_mb, zc_window_mb, hbm_cache, replay_chunk_mb,
-   *  replay_first_mb,
+   *  fast_path, one_pass, prelaunch, zero_copy, packed_h2d, pack_wait, zc_pin_budget_mb,
+   *  zc_window_mb, hbm_cache, replay_chunk_mb, replay_first_mb,
    *  shuffle_parts, shuffle_seed) */
   void Update(const std::map<std::string, std::string>& args);
 };
@@ -181,6 +201,14 @@ struct DeviceParserStats {
   double last_pass_sec{0}, last_fill_sec{0}, last_drain_sec{0};
   /*! \brief metadata waits that ended spinning / sleeping / at the bound */
   size_t waits_spun{0}, waits_slept{0}, waits_timed_out{0};
+  /*! \brief packed H2D: chunks sent as 4-bit codes / sent raw, bytes that
+   *  crossed the link, exception blocks sent with packed chunks */
+  size_t packed_chunks{0}, raw_chunks{0}, link_bytes{0}, exception_blocks{0};
+  /*! \brief packed H2D: seconds the pack pool spent packing, seconds the
+   *  submitting thread waited for a pack in progress */
+  double pack_sec{0}, wait_pack_sec{0};
+  /*! \brief packed H2D: HBM held by the per-device-slot staging buffers */
+  size_t unpack_staging_bytes{0};
 };
 
 /*!

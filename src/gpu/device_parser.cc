@@ -17,6 +17,14 @@
  * the next chunks is queued before the current chunk is parsed, so PCIe
  * transfers overlap the kernels and the reader thread fills pinned slots
  * further ahead.
+ *
+ * Packed H2D (cfg.packed_h2d, zero-copy source only): a pool of read_threads
+ * threads nibble-packs the pieces ahead of the submit cursor into pinned
+ * slots (pack_pool.h).  A piece whose pack is finished crosses the link as
+ * 4-bit codes into the device slot's staging buffer and is expanded into the
+ * slot's text (or its HBM-cache arena range) on a stream of its own, right
+ * after its copied event; its parse waits for that.  A piece whose pack has
+ * not started goes raw, as without packing.  The parse kernels see the same bytes either way.
  */
 #include <dmlc/gpu/device_parser.h>
 #include <dmlc/fault.h>
@@ -41,6 +49,8 @@
 #include "../io/uri_spec.h"
 #include "./host_wait.h"
 #include "./kernels.h"
+#include "./pack_pool.h"
+#include "./text_pack.h"
 #include "./tile_pipeline.h"
 #include "./zero_copy_source.h"
 
@@ -98,6 +108,10 @@ void DeviceParserConfig::Update(const std::map<std::string, std::string>& args) 
       shuffle_seed = std::atoi(v.c_str());
     } else if (k == "zero_copy") {
       zero_copy = (v == "auto" || v == "-1") ? -1 : ((v == "0" || v == "false") ? 0 : 1);
+    } else if (k == "pack_wait") {
+      pack_wait = v != "0" && v != "false";
+    } else if (k == "packed_h2d") {
+      packed_h2d = (v == "auto" || v == "-1") ? -1 : ((v == "0" || v == "false") ? 0 : 1);
     }
   }
   chunk_bytes = (chunk_bytes + 4095) & ~size_t(4095);
@@ -223,6 +237,11 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
       }
     }
     if (zc_ == nullptr) StartReader();
+    if (zc_ != nullptr &&
+        (cfg_.packed_h2d == 1 ||
+         (cfg_.packed_h2d < 0 && cfg_.read_threads >= 2 && cfg_.chunk_bytes >= (size_t(1) << 20)))) {
+      StartPacking();
+    }
     if (cfg_.hbm_cache) StartCaching();
   }
 
@@ -230,6 +249,7 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
     // make sure no transfer still reads a pinned slot we are about to free;
     // destructors never throw, so errors are ignored here
     if (copy_) (void)hipStreamSynchronize(copy_->get());
+    if (unpack_) (void)hipStreamSynchronize(unpack_->get());
     if (compute_) (void)hipStreamSynchronize(compute_->get());
     if (pre_.stream) (void)hipStreamSynchronize(pre_.stream->get());
     for (auto& f : inflight_) {
@@ -237,6 +257,7 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
     }
     inflight_.clear();
     iter_.Destroy();
+    pool_.reset();  // before the mappings its threads read go away
     zc_.reset();
   }
 
@@ -444,6 +465,9 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
     size_t size;
     size_t end_pos;  // resume cursor once this chunk is delivered
     const char* text;  // device text of the chunk
+    int pack_slot;     // >= 0: its H2D reads this pinned pack slot
+    bool packed;       // sent as 4-bit codes: expanded from dstage_[d] before the parse
+    uint32_t nexc;     // its exception blocks
   };
   /*! \brief a chunk held in the HBM epoch cache */
   struct CachedChunk {
@@ -524,7 +548,8 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
           end_pos = replay_end_[replay_idx_];
           ++replay_idx_;
         }
-        inflight_.push_back(Inflight{nullptr, -1, size, end_pos, arena_->get<char>() + c.off});
+        inflight_.push_back(
+            Inflight{nullptr, -1, size, end_pos, arena_->get<char>() + c.off, -1, false, 0});
       }
       reader_done_ = replay_idx_ == replay_list_.size();
       return;
@@ -536,7 +561,18 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
       HostSlot* slot = nullptr;
       const void* src = nullptr;
       size_t size = 0, end_pos = 0;
-      if (zc_ != nullptr) {
+      std::unique_ptr<PackJob> job;  // packed H2D: the piece's lookahead entry
+      if (pool_ != nullptr) {
+        job = NextPackJob();
+        if (job == nullptr) {
+          reader_done_ = true;
+          if (caching_) cache_complete_ = true;
+          break;
+        }
+        src = job->ptr;
+        size = job->size;
+        end_pos = job->end_pos;
+      } else if (zc_ != nullptr) {
         ZeroCopySource::Piece piece;
         if (!zc_->Next(&piece)) {
           reader_done_ = true;
@@ -573,7 +609,10 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
         const size_t begin_pos = cached_.empty() ? 0 : cached_.back().end_pos;
         CHECK_LE(arena_fill_ + size, arena_bytes_) << "HBM cache arena overflow";
         dst = arena_->get<char>() + arena_fill_;
-        const char last = size != 0 ? static_cast<const char*>(src)[size - 1] : '\n';
+        // (a packed piece's mapping may already be released: its last byte was kept)
+        const char last = job != nullptr ? job->last
+                          : size != 0    ? static_cast<const char*>(src)[size - 1]
+                                         : '\n';
         CachedChunk c{arena_fill_, size, begin_pos, end_pos, 0, begin_pos, end_pos,
                       last == '\n' || last == '\r'};
         if (cfg_.shuffle_parts > 1) {
@@ -589,10 +628,169 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
         arena_fill_ += size;
       }
       DMLC_HIP_CHECK(hipStreamWaitEvent(copy_->get(), parsed_[d]->get(), 0));
-      DMLC_HIP_CHECK(hipMemcpyAsync(dst, src, size, hipMemcpyHostToDevice, copy_->get()));
-      copied_[d]->Record(copy_->get());
-      inflight_.push_back(Inflight{slot, d, size, end_pos, dst});
+      int pack_slot = -1;
+      uint32_t nexc = 0;
+      const bool packed = job != nullptr && job->state.load() == PackJob::kPacked;
+      if (packed) {
+        // the codes go to the slot's staging buffer
+        if (dstage_[d] == nullptr || dstage_[d]->bytes() < job->packed_bytes) {
+          parsed_[d]->Synchronize();
+          if (dstage_[d] != nullptr) stats_.unpack_staging_bytes -= dstage_[d]->bytes();
+          dstage_[d].reset(new DeviceBuffer(
+              std::max(job->packed_bytes, PackSlotBytes(cfg_.chunk_bytes))));
+          stats_.unpack_staging_bytes += dstage_[d]->bytes();
+        }
+        DMLC_HIP_CHECK(hipMemcpyAsync(dstage_[d]->get(), job->out, job->packed_bytes,
+                                      hipMemcpyHostToDevice, copy_->get()));
+        // expanded as soon as the codes have landed, on a stream of its own:
+        // the copy stream goes straight on to the next DMA, the compute
+        // stream is not held up behind a copy, and the text (the HBM-cache
+        // arena's too) is whole even if the chunk is never parsed
+        copied_[d]->Record(copy_->get());
+        DMLC_HIP_CHECK(hipStreamWaitEvent(unpack_->get(), copied_[d]->get(), 0));
+        LaunchUnpackText(dstage_[d]->get(), size, job->nexc, alphabet_, dst, unpack_->get());
+        unpacked_[d]->Record(unpack_->get());
+        pack_slot = job->slot;
+        nexc = job->nexc;
+        stats_.packed_chunks += 1;
+        stats_.exception_blocks += nexc;
+        stats_.link_bytes += job->packed_bytes;
+      } else {
+        DMLC_HIP_CHECK(hipMemcpyAsync(dst, src, size, hipMemcpyHostToDevice, copy_->get()));
+        stats_.raw_chunks += 1;
+        stats_.link_bytes += size;
+        // a rescued piece is read from its pack slot until the copy is done
+        if (job != nullptr) {
+          if (job->rescued) {
+            pack_slot = job->slot;
+          } else {
+            free_pack_slots_.push_back(job->slot);
+          }
+        }
+        copied_[d]->Record(copy_->get());
+      }
+      inflight_.push_back(Inflight{slot, d, size, end_pos, dst, pack_slot, packed, nexc});
     }
+  }
+
+  // ------------------------------------------------------------- packed H2D
+  /*! \brief pieces fetched ahead of the submit cursor, and how close to it the
+   *  pool may still start a pack (closer pieces go raw) */
+  static constexpr size_t kPackLookahead = 4;
+  static constexpr size_t kPackDistance = 2;
+
+  void StartPacking() {
+    uint8_t alphabet[16];
+    PackAlphabet(tcfg_.format == TextFormat::kCSV, cfg_.delimiter, alphabet);
+    std::memcpy(alphabet_, alphabet, 16);
+    pack_distance_ = cfg_.pack_wait ? 0 : kPackDistance;
+    pool_.reset(new PackPool(cfg_.read_threads, alphabet, pack_distance_));
+    // a slot per lookahead entry and per packed chunk in flight
+    pack_slots_ =
+        std::vector<PinnedBuffer>(kPackLookahead + static_cast<size_t>(cfg_.device_slots) + 1);
+    for (size_t i = 0; i < pack_slots_.size(); ++i) free_pack_slots_.push_back(static_cast<int>(i));
+    dstage_.resize(static_cast<size_t>(cfg_.device_slots));
+    unpack_.reset(new Stream());
+    for (int d = 0; d < cfg_.device_slots; ++d) unpacked_.emplace_back(new Event());
+    // windowed source: before a window is released, no queued piece may still
+    // point into it and no pool thread may still read it
+    zc_->SetDrain([this]() {
+      RescueLookahead();
+      copy_->Synchronize();
+    });
+  }
+
+  /*! \brief pinned bytes a piece of n bytes needs: its packed form at the 3/4
+   *  bound, or (windowed source) its raw bytes when it has to be rescued */
+  size_t PackSlotBytes(size_t n, bool may_hold_raw = false) const {
+    const size_t packed = static_cast<size_t>(kPackMaxRatio * static_cast<double>(n)) + 64;
+    return std::max<size_t>(may_hold_raw ? std::max(packed, n) : packed, 4096);
+  }
+
+  /*! \brief fetch pieces until the lookahead is full, hand the new ones far
+   *  enough ahead to the pool, and pop the piece to submit (null at the end).
+   *  On return the piece is packed (state kPacked) or goes raw. */
+  std::unique_ptr<PackJob> NextPackJob() {
+    while (!la_end_ && la_.size() < kPackLookahead) {
+      ZeroCopySource::Piece piece;
+      if (!zc_->Next(&piece)) {
+        la_end_ = true;
+        break;
+      }
+      std::unique_ptr<PackJob> job(new PackJob());
+      job->ptr = piece.ptr;
+      job->size = piece.size;
+      job->end_pos = zc_->Tell();
+      if (piece.size != 0) job->last = piece.ptr[piece.size - 1];
+      job->seq = la_seq_++;
+      CHECK(!free_pack_slots_.empty()) << "internal error: no free pack slot";
+      job->slot = free_pack_slots_.back();
+      free_pack_slots_.pop_back();
+      PinnedBuffer& buf = pack_slots_[job->slot];
+      if (buf.bytes() < PackSlotBytes(piece.size, zc_->windowed())) {
+        buf.Reserve(PackSlotBytes(std::max(piece.size, cfg_.chunk_bytes), zc_->windowed()));
+      }
+      job->out = buf.get<uint8_t>();
+      la_.push_back(std::move(job));
+      // the first pieces of a pass go raw: the link does not wait for the pool
+      if (la_.back()->seq >= submitted_ + pack_distance_) pool_->Push(la_.back().get());
+    }
+    if (la_.empty()) return nullptr;
+    std::unique_ptr<PackJob> job = std::move(la_.front());
+    la_.pop_front();
+    pool_->SetSubmitted(++submitted_);
+    if (!job->rescued && job->state.load() != PackJob::kPacked &&
+        (cfg_.pack_wait || !pool_->TryClaimRaw(job.get()))) {
+      // its pack is in progress: the copies already queued keep the link busy
+      const double t0 = GetTime();
+      try {
+        pool_->Wait(job.get());
+      } catch (...) {
+        free_pack_slots_.push_back(job->slot);
+        throw;
+      }
+      stats_.wait_pack_sec += GetTime() - t0;
+    }
+    stats_.pack_sec = pool_->pack_sec();
+    return job;
+  }
+
+  /*! \brief the source is about to release a window: settle every queued
+   *  piece of that window so that it no longer needs the mapping (packed, or
+   *  its raw bytes copied into its slot) */
+  void RescueLookahead() {
+    for (auto& job : la_) {
+      if (job->rescued || !zc_->Releasing(job->ptr)) continue;
+      if (!pool_->TryClaimRaw(job.get())) {
+        try {
+          pool_->Wait(job.get());
+        } catch (...) {
+          job->state.store(PackJob::kRejected);  // goes raw
+        }
+      }
+      if (job->state.load() == PackJob::kPacked) continue;
+      std::memcpy(job->out, job->ptr, job->size);
+      job->ptr = reinterpret_cast<const char*>(job->out);
+      job->rescued = true;
+    }
+  }
+
+  /*! \brief forget the lookahead (Seek, a new epoch order): no pool thread
+   *  reads a piece afterwards */
+  void DropLookahead() {
+    if (pool_ == nullptr) return;
+    pool_->Quiesce();
+    for (auto& job : la_) free_pack_slots_.push_back(job->slot);
+    la_.clear();
+    la_end_ = false;
+    la_seq_ = submitted_ = 0;
+    pool_->SetSubmitted(0);
+  }
+
+  void ReleasePackSlot(int* pack_slot) {
+    if (*pack_slot < 0) return;
+    free_pack_slots_.push_back(*pack_slot);
+    *pack_slot = -1;
   }
 
   void StartCaching() {
@@ -611,12 +809,16 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
 
   void DrainInflight(bool keep_prelaunch = false) {
     copy_->Synchronize();
+    if (unpack_) unpack_->Synchronize();
     compute_->Synchronize();
     if (!keep_prelaunch) pre_.Drop();
     while (!inflight_.empty()) {
       if (inflight_.front().slot != nullptr) iter_.Recycle(&inflight_.front().slot);
+      ReleasePackSlot(&inflight_.front().pack_slot);
       inflight_.pop_front();
     }
+    ReleasePackSlot(&cur_pack_slot_);
+    DropLookahead();
     reader_done_ = false;
     busy_ = 0;
   }
@@ -935,6 +1137,7 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
   /*! \brief the H2D of the current chunk is complete: recycle and keep PCIe busy */
   void AfterFirstSync() {
     if (cur_slot_ != nullptr) iter_.Recycle(&cur_slot_);
+    ReleasePackSlot(&cur_pack_slot_);
     FillPipeline();
   }
 
@@ -952,10 +1155,15 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
     inflight_.pop_front();
     busy_ = 1;
     cur_slot_ = cur.slot;
+    cur_pack_slot_ = cur.pack_slot;
     EnsureScratch(cur.size);
     hipStream_t s = compute_->get();
     ScopedRange range("parse_chunk");
-    if (cur.d >= 0) DMLC_HIP_CHECK(hipStreamWaitEvent(s, copied_[cur.d]->get(), 0));
+    if (cur.d >= 0) {
+      // a packed chunk's text is there once its unpack (after its copy) is done
+      Event* ready = cur.packed ? unpacked_[cur.d].get() : copied_[cur.d].get();
+      DMLC_HIP_CHECK(hipStreamWaitEvent(s, ready->get(), 0));
+    }
     try {
       body(cur.text, cur.size);
       DMLC_FAULT_POINT("parse_fill");
@@ -967,6 +1175,7 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
       (void)hipStreamSynchronize(s);
       if (cur.d >= 0) (void)hipEventRecord(parsed_[cur.d]->get(), s);
       busy_ = 0;
+      ReleasePackSlot(&cur_pack_slot_);
       if (cur_slot_ != nullptr) {
         try {
           iter_.Recycle(&cur_slot_);
@@ -976,6 +1185,7 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
       throw;
     }
     if (cur_slot_ != nullptr) iter_.Recycle(&cur_slot_);
+    ReleasePackSlot(&cur_pack_slot_);
     if (cur.d >= 0) parsed_[cur.d]->Record(s);
     busy_ = 0;
     cursor_ = cur.end_pos;  // only once the chunk is delivered
@@ -1269,6 +1479,19 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
   PinnedBuffer hmeta_;
   ThreadedIter<HostSlot> iter_;
   std::unique_ptr<ZeroCopySource> zc_;
+  // packed H2D: the pool, the pieces fetched ahead of the submit cursor, the
+  // pinned pack slots and the per-device-slot staging buffers of the codes
+  std::unique_ptr<PackPool> pool_;
+  std::deque<std::unique_ptr<PackJob>> la_;
+  bool la_end_{false};
+  size_t la_seq_{0}, submitted_{0}, pack_distance_{0};
+  std::vector<PinnedBuffer> pack_slots_;
+  std::vector<int> free_pack_slots_;
+  std::vector<std::unique_ptr<DeviceBuffer>> dstage_;
+  std::unique_ptr<Stream> unpack_;
+  std::vector<std::unique_ptr<Event>> unpacked_;
+  uint8_t alphabet_[16];
+  int cur_pack_slot_{-1};
   std::deque<Inflight> inflight_;
   /*! \brief HBM epoch cache (cfg_.hbm_cache): the partition's chunks, resident */
   std::unique_ptr<DeviceBuffer> arena_;

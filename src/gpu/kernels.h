@@ -466,6 +466,14 @@ size_t CSRTransposeScratchBytes(uint64_t nnz, uint64_t num_features);
 uint64_t CSRTransposeMaxFeatures();
 /*! \brief fill n floats with v */
 void LaunchFill(float* p, size_t n, float v, hipStream_t stream);
+/*!
+ * \brief packed H2D (unpack_kernels.hip): expand the packed chunk at `packed`
+ *  (device copy of a text_pack.h chunk of n bytes with nexc exception blocks,
+ *  256-byte aligned) into exactly n text bytes at dst (any alignment); bytes
+ *  past dst + n are not written
+ */
+void LaunchUnpackText(const void* packed, size_t n, uint32_t nexc, const uint8_t alphabet[16],
+                      char* dst, hipStream_t stream);
 
 }  // namespace gpu
 }  // namespace dmlc

@@ -131,6 +131,14 @@ class ZeroCopySource {
    *  reads pieces handed out earlier (the owner's copy-stream sync)
    */
   void SetDrain(std::function<void()> drain) { drain_ = std::move(drain); }
+  /*!
+   * \brief inside the drain callback: whether the piece at p lies in a mapping
+   *  about to be released (an owner that holds pieces back, not yet submitted,
+   *  must stop using exactly those)
+   */
+  bool Releasing(const char* p) const {
+    return release_all_ || (p >= release_begin_ && p < release_end_);
+  }
   bool windowed() const { return windowed_; }
   void Reset() { Seek(0); }
   /*! \brief next chunk of whole records; false at the end */
@@ -298,7 +306,11 @@ class ZeroCopySource {
   void Rewind() {
     JoinPending();
     if (!windowed_) return;
-    if (!windows_.empty() && drain_) drain_();
+    if (!windows_.empty() && drain_) {
+      release_all_ = true;
+      drain_();
+      release_all_ = false;
+    }
     for (auto& w : windows_) Unmap(&w);
     windows_.clear();
   }
@@ -344,7 +356,12 @@ class ZeroCopySource {
     }
     // windowed: at most two windows pinned, the oldest released once its DMAs are done
     if (windowed_ && windows_.size() >= 2) {
-      if (drain_) drain_();
+      if (drain_) {
+        release_begin_ = static_cast<const char*>(windows_.front().map);
+        release_end_ = release_begin_ + windows_.front().map_len;
+        drain_();
+        release_begin_ = release_end_ = nullptr;
+      }
       Unmap(&windows_.front());
       windows_.pop_front();
     }
@@ -423,6 +440,10 @@ class ZeroCopySource {
   size_t pinned_{0}, peak_pinned_{0};
   std::future<Mapping> pending_;
   std::function<void()> drain_;
+  // the mapping the running drain callback precedes the release of
+  const char* release_begin_{nullptr};
+  const char* release_end_{nullptr};
+  bool release_all_{false};
   size_t seg_{0}, off_{0};
 };
 

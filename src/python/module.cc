@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "../gpu/kernels.h"
+#include "../gpu/text_pack.h"
 #include "../io/http.h"
 #include "../io/line_split.h"
 #include "../io/recordio_split.h"
@@ -473,6 +474,13 @@ class PyDeviceParser {
     d["waits_spun"] = s.waits_spun;
     d["waits_slept"] = s.waits_slept;
     d["waits_timed_out"] = s.waits_timed_out;
+    d["packed_chunks"] = s.packed_chunks;
+    d["raw_chunks"] = s.raw_chunks;
+    d["link_bytes"] = s.link_bytes;
+    d["exception_blocks"] = s.exception_blocks;
+    d["pack_sec"] = s.pack_sec;
+    d["wait_pack_sec"] = s.wait_pack_sec;
+    d["unpack_staging_bytes"] = s.unpack_staging_bytes;
     return d;
   }
   uintptr_t Stream() const { return reinterpret_cast<uintptr_t>(p_->stream()); }
@@ -685,11 +693,75 @@ void BindRecordIO(py::module_& m) {
       .def("stream", &PyDeviceRecordIO::Stream);
 }
 
+// ------------------------------------------------------------ packed H2D
+/*! \brief nibble-pack `text` (src/gpu/text_pack.h); None when the packed size
+ *  exceeds ratio * len(text) (the chunk would cross the link raw) */
+py::object PackTextPy(const std::string& text, const std::string& format, const std::string& delimiter,
+                      double ratio, int isa) {
+  CHECK(format == "libsvm" || format == "libfm" || format == "csv") << "unknown format " << format;
+  CHECK_EQ(delimiter.size(), 1U) << "delimiter must be one character";
+  CHECK(gpu::PackIsaSupported(static_cast<gpu::PackIsa>(isa))) << "instruction set not supported";
+  uint8_t alphabet[16];
+  gpu::PackAlphabet(format == "csv", delimiter[0], alphabet);
+  std::vector<uint8_t> packed;
+  if (!gpu::PackText(reinterpret_cast<const uint8_t*>(text.data()), text.size(), alphabet, ratio,
+                     &packed, static_cast<gpu::PackIsa>(isa))) {
+    return py::none();
+  }
+  return py::bytes(reinterpret_cast<const char*>(packed.data()), packed.size());
+}
+
+size_t CheckedPackedSize(const std::string& packed) {
+  CHECK_GE(packed.size(), sizeof(gpu::PackedHeader)) << "not a packed chunk";
+  const gpu::PackedView v = gpu::ViewPacked(reinterpret_cast<const uint8_t*>(packed.data()));
+  CHECK_EQ(v.bytes, packed.size()) << "packed chunk size mismatch";
+  for (uint32_t i = 0; i < v.header.nexc; ++i) {
+    uint32_t b;
+    std::memcpy(&b, reinterpret_cast<const uint8_t*>(v.exc_index) + 4 * i, 4);
+    CHECK_LT(static_cast<size_t>(b), gpu::PackBlocks(v.header.n)) << "exception block out of range";
+  }
+  return v.header.n;
+}
+
+/*! \brief CPU reference unpack */
+py::bytes UnpackTextReferencePy(const std::string& packed) {
+  std::string out(CheckedPackedSize(packed), '\0');
+  gpu::UnpackReference(reinterpret_cast<const uint8_t*>(packed.data()),
+                       reinterpret_cast<uint8_t*>(&out[0]));
+  return py::bytes(out);
+}
+
+/*! \brief device unpack into a buffer of dst_offset + n + pad bytes filled with
+ *  `fill`, at byte dst_offset; returns the whole buffer */
+py::bytes UnpackTextDevicePy(const std::string& packed, size_t dst_offset, size_t pad, int fill) {
+  const size_t n = CheckedPackedSize(packed);
+  const gpu::PackedView v = gpu::ViewPacked(reinterpret_cast<const uint8_t*>(packed.data()));
+  gpu::DeviceBuffer src(packed.size()), dst(dst_offset + n + pad);
+  gpu::Stream stream;
+  DMLC_HIP_CHECK(hipMemcpyAsync(src.get(), packed.data(), packed.size(), hipMemcpyHostToDevice,
+                                stream.get()));
+  DMLC_HIP_CHECK(hipMemsetAsync(dst.get(), fill, dst_offset + n + pad, stream.get()));
+  gpu::LaunchUnpackText(src.get(), n, v.header.nexc, v.header.alphabet,
+                        dst.get<char>() + dst_offset, stream.get());
+  DMLC_HIP_CHECK(hipGetLastError());
+  std::string out(dst_offset + n + pad, '\0');
+  DMLC_HIP_CHECK(hipMemcpyAsync(&out[0], dst.get(), out.size(), hipMemcpyDeviceToHost, stream.get()));
+  stream.Synchronize();
+  return py::bytes(out);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_dmlc, m) {
   m.doc() = "dmlc-core for MI355X: native runtime bindings";
   py::register_exception<dmlc::Error>(m, "DMLCError");
+  m.def("pack_text", &PackTextPy, py::arg("text"), py::arg("format") = "libsvm",
+        py::arg("delimiter") = ",", py::arg("ratio") = gpu::kPackMaxRatio, py::arg("isa") = 0);
+  m.def("pack_isa_supported",
+        [](int isa) { return gpu::PackIsaSupported(static_cast<gpu::PackIsa>(isa)); });
+  m.def("unpack_text_reference", &UnpackTextReferencePy, py::arg("packed"));
+  m.def("unpack_text_device", &UnpackTextDevicePy, py::arg("packed"), py::arg("dst_offset") = 0,
+        py::arg("pad") = 64, py::arg("fill") = 0xA5);
   py::class_<gpu::DeviceHashedBatch, std::shared_ptr<gpu::DeviceHashedBatch>>(m, "HashedBatch")
       .def_readonly("rows", &gpu::DeviceHashedBatch::rows)
       .def_readonly("row_capacity", &gpu::DeviceHashedBatch::row_cap)
