@@ -1,0 +1,525 @@
+/*!
+ * \file src/gpu/chunk_feed.cc
+ * \brief Chunk transport of the device parser (see chunk_feed.h).
+ */
+#include "./chunk_feed.h"
+
+#include <dmlc/fault.h>
+#include <dmlc/logging.h>
+#include <dmlc/timer.h>
+
+#include <algorithm>
+#include <cstring>
+
+#include "../io/filesys.h"
+#include "../io/line_split.h"
+#include "./kernels.h"
+#include "./text_pack.h"
+
+namespace dmlc {
+namespace gpu {
+
+ChunkFeed::ChunkFeed(const std::string& uri, unsigned part, unsigned nparts,
+                     const DeviceParserConfig& cfg, bool csv_alphabet, hipStream_t compute,
+                     DeviceParserStats* stats)
+    : cfg_(cfg),
+      compute_(compute),
+      stats_(stats),
+      walk_(&plan_, cfg.replay_first_bytes, cfg.replay_chunk_bytes) {
+  io::URI path(uri.c_str());
+  split_.reset(new io::LineSplitter(io::FileSystem::GetInstance(path), uri.c_str(), part, nparts));
+  if (cfg_.shuffle_parts > 1) {
+    // sub-shard i = partition part * K + i of nparts * K (record-aligned
+    // byte ranges, as InputSplitShuffle's source splits); the pipeline reads
+    // the epoch's concatenation of them
+    const unsigned k = cfg_.shuffle_parts;
+    std::vector<std::vector<EpochOrder::Segment>> subs;
+    for (unsigned i = 0; i < k; ++i) {
+      split_->ResetPartition(part * k + i, nparts * k);
+      subs.push_back(split_->ShardSegments());
+    }
+    order_ = EpochOrder(part, nparts, k, cfg_.shuffle_seed, subs);  // epoch 0
+    reader_.reset(new io::ShardReader(split_.get(), cfg_.read_threads, order_.Segments(),
+                                      order_.Stops()));
+  } else {
+    order_ = EpochOrder(part, nparts, 1, cfg_.shuffle_seed, {split_->ShardSegments()});
+    reader_.reset(new io::ShardReader(split_.get(), cfg_.read_threads));
+  }
+  copy_.reset(new Stream());
+  for (int d = 0; d < cfg_.device_slots; ++d) {
+    dtext_.emplace_back(new DeviceBuffer(cfg_.chunk_bytes + kTextPadBytes));
+    // the pad is read (never used) by 16-byte loads past the chunk end.  The
+    // memsets go on the copy stream: the streams are non-blocking, so a
+    // null-stream hipMemset is not ordered before the H2D copy into the slot
+    DMLC_HIP_CHECK(hipMemsetAsync(dtext_.back()->get(), 0, cfg_.chunk_bytes + kTextPadBytes,
+                                  copy_->get()));
+    copied_.emplace_back(new Event());
+    parsed_.emplace_back(new Event());
+    parsed_.back()->Record(compute_);
+  }
+  iter_.set_max_capacity(static_cast<size_t>(cfg_.pinned_slots));
+  if (cfg_.zero_copy != 0) {
+    zc_.reset(new ZeroCopySource());
+    const double t0 = GetTime();
+    // windowed source: before a window is released, no queued piece may still
+    // point into it, no pool thread may still read it and no DMA may
+    zc_->SetDrain([this]() {
+      RescueLookahead();
+      copy_->Synchronize();
+    });
+    stats_->zc_pin_budget = ZeroCopySource::ShardPinBudget(cfg_.zc_pin_budget);
+    if (!zc_->Init(split_.get(), cfg_.chunk_bytes, stats_->zc_pin_budget, cfg_.zc_window_bytes,
+                   order_.shuffled() ? &order_.all_segments() : nullptr)) {
+      CHECK(cfg_.zero_copy != 1) << "zero_copy=1 but the input cannot be mmap'ed + registered";
+      zc_.reset();
+    } else {
+      stats_->register_sec = GetTime() - t0;
+      stats_->zero_copy = true;
+      if (order_.shuffled()) zc_->Reorder(order_.SegmentIndices());
+    }
+  }
+  if (zc_ == nullptr) StartReader();
+  if (zc_ != nullptr &&
+      (cfg_.packed_h2d == 1 ||
+       (cfg_.packed_h2d < 0 && cfg_.read_threads >= 2 && cfg_.chunk_bytes >= (size_t(1) << 20)))) {
+    StartPacking(csv_alphabet);
+  }
+  if (cfg_.hbm_cache) StartCaching();
+}
+
+ChunkFeed::~ChunkFeed() {
+  // make sure no transfer still reads a pinned slot we are about to free;
+  // destructors never throw, so errors are ignored here
+  if (copy_) (void)hipStreamSynchronize(copy_->get());
+  if (unpack_) (void)hipStreamSynchronize(unpack_->get());
+  (void)hipStreamSynchronize(compute_);
+  for (auto& f : inflight_) {
+    if (f.slot != nullptr) iter_.Recycle(&f.slot);
+  }
+  inflight_.clear();
+  iter_.Destroy();
+  pool_.reset();  // before the mappings its threads read go away
+  zc_.reset();
+}
+
+bool ChunkFeed::SetEpoch(unsigned e) {
+  if (!order_.shuffled()) return Seek(0);
+  DrainInflight();
+  order_.Apply(e);
+  if (zc_ != nullptr) {
+    zc_->Reorder(order_.SegmentIndices());
+  } else {
+    reorder_reader_ = true;  // applied by the reader thread's rewind (Seek)
+  }
+  return Seek(0);
+}
+
+bool ChunkFeed::Seek(size_t cursor) {
+  CHECK_LE(cursor, PartitionBytes()) << "DeviceParser::Seek: cursor beyond the partition";
+  // a replay restarting at 0 keeps the next epoch's first count, prelaunched
+  // beside the last fill (NextEpochFirst; dropped if the chunk differs)
+  const bool keep_prelaunch = cursor == 0 && cache_complete_ && !order_.shuffled();
+  DrainInflight();
+  replay_ = false;
+  caching_ = false;
+  if (cfg_.hbm_cache) {
+    if (cache_complete_) {
+      // replay from the cache when the cursor is a chunk boundary of this
+      // epoch's order (sub-shards in visiting order, chunks in text order)
+      plan_.Build(order_);
+      const size_t i = plan_.FindCursor(cursor, PartitionBytes());
+      if (i != ReplayPlan::kNotABoundary) {
+        replay_ = true;
+        walk_.Start(i);
+        cursor_ = cursor;
+        return keep_prelaunch;
+      }
+    } else if (cursor == 0) {
+      StartCaching();
+    } else {
+      plan_.Clear();  // a partial pass cannot complete the cache
+      arena_fill_ = 0;
+    }
+  }
+  if (zc_ != nullptr) {
+    zc_->Seek(cursor);
+  } else {
+    seek_pos_ = cursor;
+    iter_.BeforeFirst();
+  }
+  cursor_ = cursor;
+  return keep_prelaunch;
+}
+
+void ChunkFeed::StartReader() {
+  const size_t cap = cfg_.chunk_bytes;
+  io::ShardReader* reader = reader_.get();
+  iter_.Init(
+      [reader, cap](HostSlot** dptr) {
+        if (*dptr == nullptr) {
+          *dptr = new HostSlot();
+          (*dptr)->buf.Reserve(cap + kTextPadBytes);
+          (*dptr)->cap = cap;
+        }
+        ScopedRange r("pinned_fill");
+        HostSlot* slot = *dptr;
+        size_t n = reader->Fill(slot->buf.get<char>(), slot->cap);
+        while (n == io::ShardReader::kNeedMore) {
+          // a record longer than the slot: grow it (the reader kept the bytes)
+          slot->cap = reader->NeedCapacity();
+          slot->buf.Free();
+          slot->buf.Reserve(slot->cap + kTextPadBytes);
+          n = reader->Fill(slot->buf.get<char>(), slot->cap);
+        }
+        (*dptr)->size = n;
+        (*dptr)->end_pos = reader->Tell();
+        return (*dptr)->size != 0;
+      },
+      // BeforeFirst / Seek: the consumer sets seek_pos_ before the
+      // ThreadedIter handshake, which orders it before this call
+      [this, reader]() {
+        if (reorder_reader_) {  // shuffled mode: this epoch's sub-shard order
+          reader->SetSegments(order_.Segments(), order_.Stops());
+          reorder_reader_ = false;
+        }
+        reader->Seek(seek_pos_);
+      });
+}
+
+/*! \brief the next piece of the pass from whichever source is active; false
+ *  at the end of the partition */
+bool ChunkFeed::NextPiece(Piece* out) {
+  if (pool_ != nullptr) {
+    out->job = NextPackJob();
+    if (out->job == nullptr) return false;
+    out->src = out->job->ptr;
+    out->size = out->job->size;
+    out->end_pos = out->job->end_pos;
+  } else if (zc_ != nullptr) {
+    ZeroCopySource::Piece piece;
+    if (!zc_->Next(&piece)) return false;
+    out->src = piece.ptr;
+    out->size = piece.size;
+    out->end_pos = zc_->Tell();
+  } else {
+    const double t0 = GetTime();
+    if (!iter_.Next(&out->slot)) return false;
+    stats_->wait_reader_sec += GetTime() - t0;
+    out->src = out->slot->buf.get();
+    out->size = out->slot->size;
+    out->end_pos = out->slot->end_pos;
+  }
+  return true;
+}
+
+/*! \brief HBM epoch cache: chunks are already resident, no copy and no slot */
+void ChunkFeed::FillFromCache() {
+  while (static_cast<int>(inflight_.size()) < cfg_.device_slots && !walk_.AtEnd()) {
+    // ParseAll over resident text: chunks adjacent in the arena and in this
+    // epoch's order are parsed as one larger chunk (ReplayPlan::Merge, MergeCap)
+    const ReplayPlan::Step s = walk_.Next(merge_);
+    inflight_.push_back(
+        Inflight{nullptr, -1, s.size, s.end_pos, arena_->get<char>() + s.off, -1, false});
+  }
+  reader_done_ = walk_.AtEnd();
+}
+
+/*! \brief first pass of an hbm_cache epoch: the chunk lands in its arena slot
+ *  (returned as the arena offset) */
+size_t ChunkFeed::CacheChunk(const Piece& p) {
+  const size_t begin_pos = plan_.cached_end();
+  CHECK_LE(arena_fill_ + p.size, arena_bytes_) << "HBM cache arena overflow";
+  // (a packed piece's mapping may already be released: its last byte was kept)
+  const char last = p.job != nullptr ? p.job->last
+                    : p.size != 0    ? static_cast<const char*>(p.src)[p.size - 1]
+                                     : '\n';
+  CachedChunk c{arena_fill_, p.size, begin_pos, p.end_pos, 0, 0, 0, last == '\n' || last == '\r'};
+  // the sub-shard the chunk belongs to (chunks never span two: the
+  // zero-copy pieces stop at segment ends, the pinned fills at group ends)
+  c.sub = order_.SubOf(begin_pos, &c.sub_begin);
+  c.sub_end = c.sub_begin + (p.end_pos - begin_pos);
+  CHECK_LE(c.sub_end, order_.sub_bytes(c.sub)) << "internal error: a chunk spans two sub-shards";
+  plan_.Add(c);
+  arena_fill_ += p.size;
+  return c.off;
+}
+
+/*!
+ * \brief queue H2D transfers until every device slot is in use.  The chunk
+ *  being parsed (busy_) still owns its slot: its parsed_ event has not been
+ *  recorded yet, so a copy queued into that slot would not wait for it.
+ */
+void ChunkFeed::FillPipeline() {
+  if (replay_) {
+    FillFromCache();
+    return;
+  }
+  while (static_cast<int>(inflight_.size()) + busy_ < cfg_.device_slots && !reader_done_) {
+    // fault points sit before a slot is taken, so a failure leaks nothing
+    if (zc_ != nullptr) DMLC_FAULT_POINT("read");
+    DMLC_FAULT_POINT("h2d");
+    Piece p;
+    if (!NextPiece(&p)) {
+      reader_done_ = true;
+      if (caching_) cache_complete_ = true;
+      break;
+    }
+    const PackJob* job = p.job.get();
+    const size_t size = p.size;
+    const int d = next_dslot_;
+    next_dslot_ = (next_dslot_ + 1) % cfg_.device_slots;
+    if (size + kTextPadBytes > dtext_[d]->bytes()) {
+      // a chunk longer than chunk_bytes (one long record): grow this device
+      // slot once the parse that last used it has finished
+      parsed_[d]->Synchronize();
+      dtext_[d].reset(new DeviceBuffer(size + kTextPadBytes));
+      DMLC_HIP_CHECK(hipMemsetAsync(dtext_[d]->get(), 0, size + kTextPadBytes, copy_->get()));
+    }
+    char* dst = dtext_[d]->get<char>();
+    if (caching_) dst = arena_->get<char>() + CacheChunk(p);
+    DMLC_HIP_CHECK(hipStreamWaitEvent(copy_->get(), parsed_[d]->get(), 0));
+    int pack_slot = -1;
+    const bool packed = job != nullptr && job->state.load() == PackJob::kPacked;
+    if (packed) {
+      // the codes go to the slot's staging buffer
+      if (dstage_[d] == nullptr || dstage_[d]->bytes() < job->packed_bytes) {
+        parsed_[d]->Synchronize();
+        if (dstage_[d] != nullptr) stats_->unpack_staging_bytes -= dstage_[d]->bytes();
+        dstage_[d].reset(
+            new DeviceBuffer(std::max(job->packed_bytes, PackSlotBytes(cfg_.chunk_bytes))));
+        stats_->unpack_staging_bytes += dstage_[d]->bytes();
+      }
+      DMLC_HIP_CHECK(hipMemcpyAsync(dstage_[d]->get(), job->out, job->packed_bytes,
+                                    hipMemcpyHostToDevice, copy_->get()));
+      // expanded as soon as the codes have landed, on a stream of its own:
+      // the copy stream goes straight on to the next DMA, the compute
+      // stream is not held up behind a copy, and the text (the HBM-cache
+      // arena's too) is whole even if the chunk is never parsed
+      copied_[d]->Record(copy_->get());
+      DMLC_HIP_CHECK(hipStreamWaitEvent(unpack_->get(), copied_[d]->get(), 0));
+      LaunchUnpackText(dstage_[d]->get(), size, job->nexc, alphabet_, dst, unpack_->get());
+      unpacked_[d]->Record(unpack_->get());
+      pack_slot = job->slot;
+      stats_->packed_chunks += 1;
+      stats_->exception_blocks += job->nexc;
+      stats_->link_bytes += job->packed_bytes;
+    } else {
+      DMLC_HIP_CHECK(hipMemcpyAsync(dst, p.src, size, hipMemcpyHostToDevice, copy_->get()));
+      stats_->raw_chunks += 1;
+      stats_->link_bytes += size;
+      // a rescued piece is read from its pack slot until the copy is done
+      if (job != nullptr) {
+        if (job->rescued) {
+          pack_slot = job->slot;
+        } else {
+          free_pack_slots_.push_back(job->slot);
+        }
+      }
+      copied_[d]->Record(copy_->get());
+    }
+    inflight_.push_back(Inflight{p.slot, d, size, p.end_pos, dst, pack_slot, packed});
+  }
+}
+
+// --------------------------------------------------------------- packed H2D
+void ChunkFeed::StartPacking(bool csv_alphabet) {
+  PackAlphabet(csv_alphabet, cfg_.delimiter, alphabet_);
+  pack_distance_ = cfg_.pack_wait ? 0 : kPackDistance;
+  pool_.reset(new PackPool(cfg_.read_threads, alphabet_, pack_distance_));
+  // a slot per lookahead entry and per packed chunk in flight
+  pack_slots_ =
+      std::vector<PinnedBuffer>(kPackLookahead + static_cast<size_t>(cfg_.device_slots) + 1);
+  for (size_t i = 0; i < pack_slots_.size(); ++i) free_pack_slots_.push_back(static_cast<int>(i));
+  dstage_.resize(static_cast<size_t>(cfg_.device_slots));
+  unpack_.reset(new Stream());
+  for (int d = 0; d < cfg_.device_slots; ++d) unpacked_.emplace_back(new Event());
+}
+
+/*! \brief pinned bytes a piece of n bytes needs: its packed form at the 3/4
+ *  bound, or (windowed source) its raw bytes when it has to be rescued */
+size_t ChunkFeed::PackSlotBytes(size_t n, bool may_hold_raw) const {
+  const size_t packed = static_cast<size_t>(kPackMaxRatio * static_cast<double>(n)) + 64;
+  return std::max<size_t>(may_hold_raw ? std::max(packed, n) : packed, 4096);
+}
+
+/*! \brief fetch pieces until the lookahead is full, hand the new ones far
+ *  enough ahead to the pool, and pop the piece to submit (null at the end).
+ *  On return the piece is packed (state kPacked) or goes raw. */
+std::unique_ptr<PackJob> ChunkFeed::NextPackJob() {
+  while (!la_end_ && la_.size() < kPackLookahead) {
+    ZeroCopySource::Piece piece;
+    if (!zc_->Next(&piece)) {
+      la_end_ = true;
+      break;
+    }
+    std::unique_ptr<PackJob> job(new PackJob());
+    job->ptr = piece.ptr;
+    job->size = piece.size;
+    job->end_pos = zc_->Tell();
+    if (piece.size != 0) job->last = piece.ptr[piece.size - 1];
+    job->seq = la_seq_++;
+    CHECK(!free_pack_slots_.empty()) << "internal error: no free pack slot";
+    job->slot = free_pack_slots_.back();
+    free_pack_slots_.pop_back();
+    PinnedBuffer& buf = pack_slots_[job->slot];
+    if (buf.bytes() < PackSlotBytes(piece.size, zc_->windowed())) {
+      buf.Reserve(PackSlotBytes(std::max(piece.size, cfg_.chunk_bytes), zc_->windowed()));
+    }
+    job->out = buf.get<uint8_t>();
+    la_.push_back(std::move(job));
+    // the first pieces of a pass go raw: the link does not wait for the pool
+    if (la_.back()->seq >= submitted_ + pack_distance_) pool_->Push(la_.back().get());
+  }
+  if (la_.empty()) return nullptr;
+  std::unique_ptr<PackJob> job = std::move(la_.front());
+  la_.pop_front();
+  pool_->SetSubmitted(++submitted_);
+  if (!job->rescued && job->state.load() != PackJob::kPacked &&
+      (cfg_.pack_wait || !pool_->TryClaimRaw(job.get()))) {
+    // its pack is in progress: the copies already queued keep the link busy
+    const double t0 = GetTime();
+    try {
+      pool_->Wait(job.get());
+    } catch (...) {
+      free_pack_slots_.push_back(job->slot);
+      throw;
+    }
+    stats_->wait_pack_sec += GetTime() - t0;
+  }
+  stats_->pack_sec = pool_->pack_sec();
+  return job;
+}
+
+/*! \brief the source is about to release a window: settle every queued
+ *  piece of that window so that it no longer needs the mapping (packed, or
+ *  its raw bytes copied into its slot).  Nothing is queued without the pool */
+void ChunkFeed::RescueLookahead() {
+  for (auto& job : la_) {
+    if (job->rescued || !zc_->Releasing(job->ptr)) continue;
+    if (!pool_->TryClaimRaw(job.get())) {
+      try {
+        pool_->Wait(job.get());
+      } catch (...) {
+        job->state.store(PackJob::kRejected);  // goes raw
+      }
+    }
+    if (job->state.load() == PackJob::kPacked) continue;
+    std::memcpy(job->out, job->ptr, job->size);
+    job->ptr = reinterpret_cast<const char*>(job->out);
+    job->rescued = true;
+  }
+}
+
+/*! \brief forget the lookahead (Seek, a new epoch order): no pool thread
+ *  reads a piece afterwards */
+void ChunkFeed::DropLookahead() {
+  if (pool_ == nullptr) return;
+  pool_->Quiesce();
+  for (auto& job : la_) free_pack_slots_.push_back(job->slot);
+  la_.clear();
+  la_end_ = false;
+  la_seq_ = submitted_ = 0;
+  pool_->SetSubmitted(0);
+}
+
+void ChunkFeed::ReleasePackSlot(int* pack_slot) {
+  if (*pack_slot < 0) return;
+  free_pack_slots_.push_back(*pack_slot);
+  *pack_slot = -1;
+}
+
+void ChunkFeed::StartCaching() {
+  plan_.Clear();
+  arena_fill_ = 0;
+  cache_complete_ = false;
+  if (arena_ == nullptr) {
+    // + the '\n' the pinned reader inserts after a segment whose last line
+    // has no EOL (one per segment at most)
+    arena_bytes_ =
+        PartitionBytes() + std::max(split_->files().size(), order_.all_segments().size()) + 16;
+    arena_.reset(new DeviceBuffer(arena_bytes_ + kTextPadBytes));
+    DMLC_HIP_CHECK(hipMemsetAsync(arena_->get(), 0, arena_bytes_ + kTextPadBytes, copy_->get()));
+  }
+  caching_ = true;
+}
+
+void ChunkFeed::DrainInflight() {
+  copy_->Synchronize();
+  if (unpack_) unpack_->Synchronize();
+  DMLC_HIP_CHECK(hipStreamSynchronize(compute_));
+  while (!inflight_.empty()) {
+    if (inflight_.front().slot != nullptr) iter_.Recycle(&inflight_.front().slot);
+    ReleasePackSlot(&inflight_.front().pack_slot);
+    inflight_.pop_front();
+  }
+  ReleasePackSlot(&cur_.pack_slot);
+  DropLookahead();
+  reader_done_ = false;
+  busy_ = 0;
+}
+
+bool ChunkFeed::Acquire(Chunk* out) {
+  FillPipeline();
+  if (inflight_.empty()) return false;
+  cur_ = inflight_.front();
+  inflight_.pop_front();
+  busy_ = 1;
+  if (cur_.d >= 0) {
+    // a packed chunk's text is there once its unpack (after its copy) is done
+    Event* ready = cur_.packed ? unpacked_[cur_.d].get() : copied_[cur_.d].get();
+    DMLC_HIP_CHECK(hipStreamWaitEvent(compute_, ready->get(), 0));
+  }
+  out->text = cur_.text;
+  out->size = cur_.size;
+  out->resident = cur_.d < 0;
+  return true;
+}
+
+void ChunkFeed::FirstSyncDone() {
+  if (cur_.slot != nullptr) iter_.Recycle(&cur_.slot);
+  ReleasePackSlot(&cur_.pack_slot);
+  FillPipeline();
+}
+
+void ChunkFeed::Release(bool delivered) {
+  if (!delivered) {
+    (void)hipStreamSynchronize(compute_);
+    if (cur_.d >= 0) (void)hipEventRecord(parsed_[cur_.d]->get(), compute_);
+    busy_ = 0;
+    ReleasePackSlot(&cur_.pack_slot);
+    if (cur_.slot != nullptr) {
+      try {
+        iter_.Recycle(&cur_.slot);
+      } catch (...) {
+      }
+    }
+    return;
+  }
+  if (cur_.slot != nullptr) iter_.Recycle(&cur_.slot);
+  ReleasePackSlot(&cur_.pack_slot);
+  if (cur_.d >= 0) parsed_[cur_.d]->Record(compute_);
+  busy_ = 0;
+  cursor_ = cur_.end_pos;  // only once the chunk is delivered
+  stats_->bytes += cur_.size;
+  stats_->chunks += 1;
+  if (zc_ != nullptr) stats_->zc_pinned_peak = zc_->PeakPinnedBytes();
+}
+
+bool ChunkFeed::PeekNextResident(const char** text, size_t* size) const {
+  if (inflight_.empty() || inflight_.front().d >= 0) return false;
+  *text = inflight_.front().text;
+  *size = inflight_.front().size;
+  return true;
+}
+
+bool ChunkFeed::NextEpochFirst(const char** text, size_t* size) const {
+  if (!replay_ || !inflight_.empty() || !reader_done_ || order_.shuffled()) return false;
+  ReplayPlan::Step s;
+  if (!walk_.NextEpochFirst(merge_, &s) || s.size == 0) return false;
+  *text = arena_->get<char>() + s.off;
+  *size = s.size;
+  return true;
+}
+
+}  // namespace gpu
+}  // namespace dmlc
