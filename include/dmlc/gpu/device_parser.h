@@ -204,9 +204,10 @@ struct DeviceParserStats {
   /*! \brief packed H2D: chunks sent as 4-bit codes / sent raw, bytes that
    *  crossed the link, exception blocks sent with packed chunks */
   size_t packed_chunks{0}, raw_chunks{0}, link_bytes{0}, exception_blocks{0};
-  /*! \brief packed H2D: seconds the pack pool spent packing, seconds the
-   *  submitting thread waited for a pack in progress */
-  double pack_sec{0}, wait_pack_sec{0};
+  /*! \brief packed H2D: wall seconds the pack pool had a job open, seconds the
+   *  submitting thread waited for a pack, and the part of those waits that
+   *  began with no copy outstanding (link time lost to the pool) */
+  double pack_sec{0}, wait_pack_sec{0}, wait_pack_idle_sec{0};
   /*! \brief packed H2D: HBM held by the per-device-slot staging buffers */
   size_t unpack_staging_bytes{0};
 };

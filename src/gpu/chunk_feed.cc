@@ -255,6 +255,10 @@ void ChunkFeed::FillPipeline() {
     return;
   }
   while (static_cast<int>(inflight_.size()) + busy_ < cfg_.device_slots && !reader_done_) {
+    // the next piece's pack is not finished and the link has work: the parse
+    // goes on with what is queued, and the piece is looked at again at the
+    // next call (never with nothing queued: PreparePackJob)
+    if (pool_ != nullptr && !PreparePackJob()) break;
     // fault points sit before a slot is taken, so a failure leaks nothing
     if (zc_ != nullptr) DMLC_FAULT_POINT("read");
     DMLC_FAULT_POINT("h2d");
@@ -317,6 +321,7 @@ void ChunkFeed::FillPipeline() {
       }
       copied_[d]->Record(copy_->get());
     }
+    last_copy_d_ = d;
     inflight_.push_back(Inflight{p.slot, d, size, p.end_pos, dst, pack_slot, packed});
   }
 }
@@ -324,8 +329,8 @@ void ChunkFeed::FillPipeline() {
 // --------------------------------------------------------------- packed H2D
 void ChunkFeed::StartPacking(bool csv_alphabet) {
   PackAlphabet(csv_alphabet, cfg_.delimiter, alphabet_);
-  pack_distance_ = cfg_.pack_wait ? 0 : kPackDistance;
-  pool_.reset(new PackPool(cfg_.read_threads, alphabet_, pack_distance_));
+  // the pool packs every queued piece, the one nearest the cursor first
+  pool_.reset(new PackPool(cfg_.read_threads, alphabet_, /*distance=*/0));
   // a slot per lookahead entry and per packed chunk in flight
   pack_slots_ =
       std::vector<PinnedBuffer>(kPackLookahead + static_cast<size_t>(cfg_.device_slots) + 1);
@@ -342,10 +347,14 @@ size_t ChunkFeed::PackSlotBytes(size_t n, bool may_hold_raw) const {
   return std::max<size_t>(may_hold_raw ? std::max(packed, n) : packed, 4096);
 }
 
-/*! \brief fetch pieces until the lookahead is full, hand the new ones far
- *  enough ahead to the pool, and pop the piece to submit (null at the end).
- *  On return the piece is packed (state kPacked) or goes raw. */
-std::unique_ptr<PackJob> ChunkFeed::NextPackJob() {
+/*! \brief an H2D copy queued earlier in this pass is still outstanding */
+bool ChunkFeed::LinkBusy() const { return last_copy_d_ >= 0 && !copied_[last_copy_d_]->Query(); }
+
+/*! \brief fetch pieces until the lookahead is full, hand them to the pool and
+ *  decide what becomes of the piece at the submit cursor (DecideSubmit).
+ *  false: it is left to the pool while the link has work (try again at the
+ *  next call); true: NextPackJob carries the decision out */
+bool ChunkFeed::PreparePackJob() {
   while (!la_end_ && la_.size() < kPackLookahead) {
     ZeroCopySource::Piece piece;
     if (!zc_->Next(&piece)) {
@@ -367,16 +376,61 @@ std::unique_ptr<PackJob> ChunkFeed::NextPackJob() {
     }
     job->out = buf.get<uint8_t>();
     la_.push_back(std::move(job));
-    // the first pieces of a pass go raw: the link does not wait for the pool
-    if (la_.back()->seq >= submitted_ + pack_distance_) pool_->Push(la_.back().get());
   }
+  if (la_.empty()) return true;
+  PackJob* job = la_.front().get();
+  const int state = job->state.load();
+  next_action_ = job->rescued ? SubmitAction::kSubmit
+                              : DecideSubmit(state, cfg_.pack_wait != 0,
+                                             inflight_.empty(), pool_behind_,
+                                             [this]() { return LinkBusy(); });
+  if (pool_behind_ && !job->rescued) {
+    // the pool has caught up once kPackCaughtUp pieces in a row were found
+    // packed at the cursor
+    packed_in_a_row_ = state == PackJob::kPacked ? packed_in_a_row_ + 1 : 0;
+    if (packed_in_a_row_ >= kPackCaughtUp) SetPoolBehind(false);
+  }
+  // the new pieces go to the pool in file order, only now: a piece fetched
+  // straight to the cursor (the first of a pass) that goes raw is never
+  // pushed, so the pool cannot have started it
+  if (la_pushed_ == 0 && next_action_ == SubmitAction::kClaimRaw) {
+    front_unpushed_ = true;
+    la_pushed_ = 1;
+  } else if (front_unpushed_ && next_action_ != SubmitAction::kClaimRaw) {
+    front_unpushed_ = false;
+    if (job->state.load() == PackJob::kQueued) pool_->Push(job);
+  }
+  for (; la_pushed_ < la_.size(); ++la_pushed_) {
+    // (a piece rescued while it was fetched is settled already)
+    if (la_[la_pushed_]->state.load() == PackJob::kQueued) pool_->Push(la_[la_pushed_].get());
+  }
+  return next_action_ != SubmitAction::kDefer;
+}
+
+/*! \brief the pool's rate is below what the link takes (it made the link wait),
+ *  or it has caught up.  Behind, the pool leaves the pieces next to the cursor
+ *  alone and they go raw, which adds the link's rate to half the pool's;
+ *  otherwise it packs everything and only the first piece of a pass goes raw */
+void ChunkFeed::SetPoolBehind(bool behind) {
+  pool_behind_ = behind;
+  packed_in_a_row_ = 0;
+  pool_->SetDistance(behind ? kPackDistance : 0);
+}
+
+/*! \brief pop the piece PreparePackJob decided on (null at the end of the
+ *  partition).  On return it is packed (state kPacked) or goes raw. */
+std::unique_ptr<PackJob> ChunkFeed::NextPackJob() {
   if (la_.empty()) return nullptr;
   std::unique_ptr<PackJob> job = std::move(la_.front());
   la_.pop_front();
+  --la_pushed_;
+  front_unpushed_ = false;
   pool_->SetSubmitted(++submitted_);
-  if (!job->rescued && job->state.load() != PackJob::kPacked &&
-      (cfg_.pack_wait || !pool_->TryClaimRaw(job.get()))) {
-    // its pack is in progress: the copies already queued keep the link busy
+  if (next_action_ == SubmitAction::kClaimRaw && !pool_->TryClaimRaw(job.get())) {
+    next_action_ = SubmitAction::kWait;  // the pool got there first
+  }
+  if (next_action_ == SubmitAction::kWait) {
+    const bool idle = !LinkBusy();
     const double t0 = GetTime();
     try {
       pool_->Wait(job.get());
@@ -385,6 +439,11 @@ std::unique_ptr<PackJob> ChunkFeed::NextPackJob() {
       throw;
     }
     stats_->wait_pack_sec += GetTime() - t0;
+    if (idle) {
+      stats_->wait_pack_idle_sec += GetTime() - t0;
+      // the link stood still for the pool: the pool cannot feed it alone
+      if (!cfg_.pack_wait) SetPoolBehind(true);
+    }
   }
   stats_->pack_sec = pool_->pack_sec();
   return job;
@@ -418,7 +477,8 @@ void ChunkFeed::DropLookahead() {
   for (auto& job : la_) free_pack_slots_.push_back(job->slot);
   la_.clear();
   la_end_ = false;
-  la_seq_ = submitted_ = 0;
+  front_unpushed_ = false;
+  la_seq_ = submitted_ = la_pushed_ = 0;
   pool_->SetSubmitted(0);
 }
 
@@ -454,6 +514,7 @@ void ChunkFeed::DrainInflight() {
   }
   ReleasePackSlot(&cur_.pack_slot);
   DropLookahead();
+  last_copy_d_ = -1;
   reader_done_ = false;
   busy_ = 0;
 }

@@ -25,8 +25,15 @@
  *   copy stream    : wait(parsed[d]) -> H2D(stage[d]) -> record(copied[d])
  *   unpack stream  : wait(copied[d]) -> unpack -> record(unpacked[d])
  *   compute stream : wait(unpacked[d]) -> parse -> record(parsed[d])
- * A piece whose pack has not started goes raw, as without packing.  The parse
- * kernels see the same bytes either way.
+ * A piece whose pack is not finished goes raw only when the link would
+ * otherwise idle (pack_pool.h, DecideSubmit), on the same copy stream:
+ *   copy stream    : wait(parsed[d]) -> H2D(text[d]) -> record(copied[d])
+ * The first piece of a pass does.  While copied[] of the last submitted chunk
+ * is still outstanding, the piece is left to the pool and FillPipeline returns
+ * with a device slot unfilled; Acquire, FirstSyncDone and the next Acquire try
+ * again.  If the link ever has to wait for a pack, the pool is slower than the
+ * link: until it has caught up, unstarted pieces next to the cursor go raw at
+ * once.  The parse kernels see the same bytes either way.
  *
  * HBM epoch cache (cfg.hbm_cache): the first full pass lands every chunk in
  * one device arena; later epochs replay it from there in the epoch's order
@@ -173,10 +180,12 @@ class ChunkFeed {
     size_t size{0}, end_pos{0};
     std::unique_ptr<PackJob> job;  // packed H2D: the piece's lookahead entry
   };
-  /*! \brief pieces fetched ahead of the submit cursor, and how close to it the
-   *  pool may still start a pack (closer pieces go raw) */
+  /*! \brief pieces fetched ahead of the submit cursor; while the pool is
+   *  behind the link, how close to the cursor it may still start a pack (closer
+   *  pieces go raw) and how many pieces found packed in a row end that state */
   static constexpr size_t kPackLookahead = 4;
   static constexpr size_t kPackDistance = 2;
+  static constexpr size_t kPackCaughtUp = 8;
 
   void StartReader();
   void StartPacking(bool csv_alphabet);
@@ -186,6 +195,9 @@ class ChunkFeed {
   bool NextPiece(Piece* out);
   size_t CacheChunk(const Piece& p);
   size_t PackSlotBytes(size_t n, bool may_hold_raw = false) const;
+  bool LinkBusy() const;
+  bool PreparePackJob();
+  void SetPoolBehind(bool behind);
   std::unique_ptr<PackJob> NextPackJob();
   void RescueLookahead();
   void DropLookahead();
@@ -208,7 +220,19 @@ class ChunkFeed {
   std::unique_ptr<PackPool> pool_;
   std::deque<std::unique_ptr<PackJob>> la_;
   bool la_end_{false};
-  size_t la_seq_{0}, submitted_{0}, pack_distance_{0};
+  size_t la_seq_{0}, submitted_{0};
+  /*! \brief leading entries of la_ the pool has been handed; the front one may
+   *  have been held back because it goes raw (front_unpushed_) */
+  size_t la_pushed_{0};
+  bool front_unpushed_{false};
+  /*! \brief the submit thread had to wait for a pack with the link idle, and
+   *  the pool has not caught up since (kept across passes) */
+  bool pool_behind_{false};
+  size_t packed_in_a_row_{0};
+  /*! \brief PreparePackJob's decision for the front piece */
+  SubmitAction next_action_{SubmitAction::kSubmit};
+  /*! \brief device slot of the last chunk submitted in this pass (-1: none) */
+  int last_copy_d_{-1};
   std::vector<PinnedBuffer> pack_slots_;
   std::vector<int> free_pack_slots_;
   std::vector<std::unique_ptr<DeviceBuffer>> dstage_;

@@ -1,18 +1,26 @@
 /*!
  * \file src/gpu/pack_pool.h
  * \brief Thread pool that nibble-packs upcoming text pieces (text_pack.h) into
- *  pinned slots ahead of the H2D submit cursor.  The pool works cooperatively
- *  on one piece at a time: every thread packs a contiguous block range into
- *  the nibble area's fixed positions, the per-thread exception lists are
- *  concatenated afterwards.
+ *  pinned slots ahead of the H2D submit cursor, and the rule by which the
+ *  submit loop sends a piece packed or raw (DecideSubmit).
+ *
+ * The pool packs the queue front.  A job is cut into ranges of `range_blocks`
+ * 256-byte blocks which the threads claim with an atomic cursor; a thread that
+ * finds no range left in an open job moves straight on to the next queued one
+ * (two jobs are open at most), and the thread that reports a job's last range
+ * done writes its header and exception indices and settles it; a long list of
+ * exception blocks is copied in ranges claimed the same way first.  No thread
+ * waits for another.  The exception lists are kept per range and
+ * concatenated in range order, so a job's packed bytes equal PackText of the
+ * same input whatever the thread count or the timing.
  *
  * The consumer queues jobs in file order (Push), and at submit time either
- * finds a job packed, claims a job the pool has not started (TryClaimRaw: the
- * piece goes over the link raw, the pool skips it), or waits for the pack in
- * progress (Wait).  The pool skips jobs closer than `distance` pieces to the
- * submit cursor (they stay unstarted and go raw), so the link is not made to
- * wait for work started too late.  With distance 0 it packs every job and the
- * consumer waits for each (never claiming one raw).
+ * finds a job settled, claims a job the pool has not started (TryClaimRaw: the
+ * piece goes over the link raw, the pool never touches it), or waits for the
+ * pack in progress (Wait).  With a non-zero distance (SetDistance) the pool
+ * leaves jobs closer than that many pieces to the submit cursor unstarted, for
+ * a consumer that claims them raw because the pool cannot keep up with the
+ * link; with distance 0 it packs every job.
  */
 #ifndef DMLC_SRC_GPU_PACK_POOL_H_
 #define DMLC_SRC_GPU_PACK_POOL_H_
@@ -60,25 +68,69 @@ struct PackJob {
   bool rescued{false};
 };
 
+/*! \brief what the submit loop does with the piece at its cursor */
+enum class SubmitAction : int {
+  /*! \brief the job is settled: packed it crosses the link as codes, rejected raw */
+  kSubmit = 0,
+  /*! \brief TryClaimRaw and send it raw (if the pool got there first: kWait) */
+  kClaimRaw,
+  /*! \brief block until the pool has settled it */
+  kWait,
+  /*! \brief leave it to the pool and come back at the next call */
+  kDefer
+};
+
+/*!
+ * \brief the link-aware rule: a piece whose pack has not finished goes raw only
+ *  when the link would otherwise idle.  While a copy queued earlier is still
+ *  outstanding the piece is left to the pool (kDefer); with the link idle an
+ *  unstarted job is claimed raw and a pack in progress is waited for.
+ * \param state the job's PackJob::State
+ * \param pack_wait wait for every pack (only the 3/4 rule sends a piece raw)
+ * \param nothing_inflight no chunk is queued for the parse: the caller has to
+ *  produce one, so the piece is never deferred
+ * \param pool_behind the pool has made the link wait and not caught up since:
+ *  nothing is deferred, an unstarted piece goes raw at once, so that link and
+ *  pool work side by side (deferring a pack in progress here was measured: the
+ *  link then idles until the pack is done and the pool never catches up)
+ * \param link_busy callable: an H2D copy queued earlier is still outstanding
+ *  (asked only when the answer decides)
+ */
+template <typename LinkBusy>
+inline SubmitAction DecideSubmit(int state, bool pack_wait, bool nothing_inflight,
+                                 bool pool_behind, LinkBusy&& link_busy) {
+  if (state == PackJob::kFailed) return SubmitAction::kWait;  // Wait rethrows the pool's error
+  if (state != PackJob::kQueued && state != PackJob::kPacking) return SubmitAction::kSubmit;
+  if (pack_wait) return SubmitAction::kWait;
+  if (!nothing_inflight && !pool_behind && link_busy()) return SubmitAction::kDefer;
+  return state == PackJob::kQueued ? SubmitAction::kClaimRaw : SubmitAction::kWait;
+}
+
 class PackPool {
  public:
-  PackPool(int threads, const uint8_t alphabet[16], size_t distance)
-      : nthreads_(std::max(threads, 1)), distance_(distance), exc_(nthreads_) {
+  /*! \brief blocks per range: 256 KiB of text */
+  static constexpr size_t kRangeBlocks = 1024;
+  /*! \brief exception blocks per range of the copy that follows the pack */
+  static constexpr size_t kCopyBlocks = 1024;
+
+  PackPool(int threads, const uint8_t alphabet[16], size_t distance,
+           size_t range_blocks = kRangeBlocks)
+      : nthreads_(std::max(threads, 1)),
+        distance_(distance),
+        range_blocks_(std::max<size_t>(range_blocks, 1)),
+        encoder_(alphabet) {
     std::memcpy(alphabet_, alphabet, 16);
-    for (int t = 0; t < nthreads_; ++t) {
-      workers_.emplace_back([this, t]() { t == 0 ? Lead() : Help(t); });
-    }
+    for (int t = 0; t < nthreads_; ++t) workers_.emplace_back([this]() { Work(); });
   }
   ~PackPool() {
     {
-      // the helpers finish the current job first: the leader waits for them
+      // the open jobs are finished first
       std::unique_lock<std::mutex> lk(mu_);
       queue_.clear();
-      cv_done_.wait(lk, [&] { return current_ == nullptr; });
+      cv_done_.wait(lk, [&] { return nopen_ == 0; });
       stop_ = true;
     }
     cv_work_.notify_all();
-    cv_part_.notify_all();
     for (auto& w : workers_) w.join();
   }
   PackPool(const PackPool&) = delete;
@@ -93,6 +145,8 @@ class PackPool {
     }
     cv_work_.notify_all();
   }
+  /*! \brief from the next job opened on, skip jobs closer than this to the cursor */
+  void SetDistance(size_t distance) { distance_.store(distance, std::memory_order_relaxed); }
   /*! \brief the submit cursor: pieces submitted so far in this pass */
   void SetSubmitted(size_t n) { submitted_.store(n, std::memory_order_relaxed); }
   /*! \brief true: the pool had not started the job and will not */
@@ -120,148 +174,224 @@ class PackPool {
       LOG(FATAL) << "text pack failed";
     }
   }
-  /*! \brief drop every queued job and wait until no thread reads or writes one */
+  /*! \brief drop every queued job and wait until no thread reads or writes one
+   *  (the open jobs are finished) */
   void Quiesce() {
     std::unique_lock<std::mutex> lk(mu_);
     queue_.clear();
-    cv_done_.wait(lk, [&] { return current_ == nullptr; });
+    cv_done_.wait(lk, [&] { return nopen_ == 0; });
     error_ = nullptr;
   }
-  /*! \brief cumulative seconds the pool spent packing */
+  /*! \brief cumulative wall seconds during which at least one job was open */
   double pack_sec() const { return pack_sec_.load(std::memory_order_relaxed); }
 
  private:
-  /*! \brief blocks [begin, end) of part p of `parts` */
-  static void PartRange(size_t blocks, int parts, int p, size_t* begin, size_t* end) {
-    *begin = blocks * static_cast<size_t>(p) / parts;
-    *end = blocks * static_cast<size_t>(p + 1) / parts;
+  /*! \brief a job being packed.  A thread may touch an Open (and its job) only
+   *  under mu_ or while it holds a claimed range it has not reported done: the
+   *  job is settled, and the Open reused, only after every range is reported */
+  struct Open {
+    PackJob* job{nullptr};
+    size_t nranges{0};
+    /*! \brief order of opening: the older job's ranges are claimed first */
+    size_t order{0};
+    long exc_limit{0};
+    std::atomic<size_t> next{0}, done{0};
+    std::atomic<long> exc_total{0};
+    std::atomic<bool> fits{true};
+    /*! \brief exception blocks per range (entries keep their capacity) */
+    std::vector<std::vector<uint32_t>> exc;
+    std::vector<uint32_t> all;
+    /*! \brief the ranges are now those of the exception blocks' copy */
+    bool copying{false};
+    int result{PackJob::kRejected};
+    std::exception_ptr err;  // under mu_
+  };
+  static constexpr int kOpenJobs = 2;
+
+  /*! \brief under mu_: a range of an open job, the older job first */
+  Open* ClaimLocked(size_t* range) {
+    Open* order[kOpenJobs] = {&open_[0], &open_[1]};
+    if (order[1]->job != nullptr && (order[0]->job == nullptr || order[1]->order < order[0]->order)) {
+      std::swap(order[0], order[1]);
+    }
+    for (Open* o : order) {
+      if (o->job == nullptr || o->next.load(std::memory_order_relaxed) >= o->nranges) continue;
+      const size_t r = o->next.fetch_add(1);
+      if (r < o->nranges) {
+        *range = r;
+        return o;
+      }
+    }
+    return nullptr;
   }
-  void PackPart(PackJob* job, int p) {
-    size_t b0, b1;
-    PartRange(PackBlocks(job->size), parts_, p, &b0, &b1);
-    exc_[p].clear();
-    if (!fits_.load(std::memory_order_relaxed)) return;
-    if (!PackRange(reinterpret_cast<const uint8_t*>(job->ptr), job->size, b0, b1, alphabet_,
-                   job->out + sizeof(PackedHeader), &exc_[p], &exc_total_, exc_limit_)) {
-      fits_.store(false, std::memory_order_relaxed);
+  /*! \brief under mu_: open the queue front in a free slot; false: nothing to open */
+  bool OpenLocked() {
+    Open* o = open_[0].job == nullptr ? &open_[0] : open_[1].job == nullptr ? &open_[1] : nullptr;
+    while (o != nullptr && !queue_.empty()) {
+      PackJob* job = queue_.front();
+      queue_.pop_front();
+      // too close to the submit cursor: left unstarted for the consumer to claim
+      const size_t distance = distance_.load(std::memory_order_relaxed);
+      if (distance != 0 && job->seq < submitted_.load(std::memory_order_relaxed) + distance) {
+        continue;
+      }
+      int expect = PackJob::kQueued;
+      if (!job->state.compare_exchange_strong(expect, PackJob::kPacking)) continue;
+      o->job = job;
+      o->nranges = std::max<size_t>(1, (PackBlocks(job->size) + range_blocks_ - 1) / range_blocks_);
+      o->order = ++opened_;
+      o->exc_limit = PackMaxExceptions(job->size, job->ratio);
+      o->next.store(0);
+      o->done.store(0);
+      o->exc_total.store(0);
+      o->fits.store(o->exc_limit >= 0);
+      if (o->exc.size() < o->nranges) o->exc.resize(o->nranges);
+      o->err = nullptr;
+      o->copying = false;
+      o->result = PackJob::kRejected;
+      try {
+        DMLC_FAULT_POINT("pack");  // under mu_: the k-th pass is the k-th job
+      } catch (...) {
+        o->err = std::current_exception();
+        o->fits.store(false);
+      }
+      if (nopen_++ == 0) open_since_ = GetTime();
+      return true;
+    }
+    return false;
+  }
+  void RunRange(Open* o, size_t r) {
+    const PackJob* job = o->job;
+    const uint8_t* text = reinterpret_cast<const uint8_t*>(job->ptr);
+    if (o->copying) {
+      PackCopyExceptions(text, job->size, o->all, r * kCopyBlocks,
+                         std::min(o->all.size(), (r + 1) * kCopyBlocks), job->out);
+      return;
+    }
+    std::vector<uint32_t>& exc = o->exc[r];
+    exc.clear();
+    if (!o->fits.load(std::memory_order_relaxed)) return;
+    const size_t b0 = r * range_blocks_;
+    const size_t b1 = std::min(PackBlocks(job->size), b0 + range_blocks_);
+    if (!PackRange(text, job->size, b0, b1, encoder_, job->out + sizeof(PackedHeader), &exc,
+                   &o->exc_total, o->exc_limit)) {
+      o->fits.store(false, std::memory_order_relaxed);
     }
   }
-  /*! \brief thread 0: takes the jobs, shares each with the helpers, finishes it */
-  void Lead() {
+  /*! \brief every range of the pack is reported and this thread alone holds
+   *  the job: write the header and the exception indices.  true: the copy of
+   *  the exception blocks is opened as ranges of its own and the caller holds
+   *  the first; false: the job is ready to be settled (o->result) */
+  bool FinishPack(Open* o) {
+    PackJob* job = o->job;
+    if (!o->fits.load()) return false;
+    try {
+      o->all.clear();
+      for (size_t r = 0; r < o->nranges; ++r) {
+        o->all.insert(o->all.end(), o->exc[r].begin(), o->exc[r].end());
+      }
+      if (static_cast<long>(o->all.size()) > o->exc_limit) return false;
+      job->packed_bytes = PackFinishHeader(job->size, alphabet_, o->all, job->out);
+      job->nexc = static_cast<uint32_t>(o->all.size());
+      o->result = PackJob::kPacked;
+      const size_t ncopy = (o->all.size() + kCopyBlocks - 1) / kCopyBlocks;
+      if (ncopy <= 1) {
+        PackCopyExceptions(reinterpret_cast<const uint8_t*>(job->ptr), job->size, o->all, 0,
+                           o->all.size(), job->out);
+        return false;
+      }
+      {
+        std::lock_guard<std::mutex> lk(mu_);
+        o->copying = true;
+        o->nranges = ncopy;
+        o->done.store(0);
+        o->next.store(1);  // range 0 is the caller's
+      }
+      cv_work_.notify_all();
+      return true;
+    } catch (...) {
+      std::lock_guard<std::mutex> lk(mu_);
+      if (!o->err) o->err = std::current_exception();
+      return false;
+    }
+  }
+  void Settle(Open* o) {
+    {
+      std::lock_guard<std::mutex> lk(mu_);
+      int result = o->result;
+      if (o->err) {
+        error_ = o->err;
+        result = PackJob::kFailed;
+      }
+      o->job->state.store(result);
+      o->job = nullptr;  // from here on the pool holds no pointer to the job
+      if (--nopen_ == 0) {
+        pack_sec_.store(pack_sec_.load(std::memory_order_relaxed) + (GetTime() - open_since_),
+                        std::memory_order_relaxed);
+      }
+    }
+    cv_done_.notify_all();
+    cv_work_.notify_all();  // a slot is free for the next queued job
+  }
+  void Work() {
     for (;;) {
-      PackJob* job = nullptr;
+      Open* o = nullptr;
+      size_t r = 0;
       {
         std::unique_lock<std::mutex> lk(mu_);
-        cv_work_.wait(lk, [&] { return stop_ || !queue_.empty(); });
-        if (stop_) return;
-        job = queue_.front();
-        queue_.pop_front();
-        // too close to the submit cursor: left unstarted, it goes raw.  With
-        // distance 0 the consumer waits for every job (it never claims one),
-        // so none may be skipped, however far the cursor has come
-        if (distance_ != 0 && job->seq < submitted_.load(std::memory_order_relaxed) + distance_) {
-          continue;
-        }
-        int expect = PackJob::kQueued;
-        if (!job->state.compare_exchange_strong(expect, PackJob::kPacking)) continue;
-        current_ = job;
-        exc_limit_ = PackMaxExceptions(job->size, job->ratio);
-        exc_total_.store(0);
-        fits_.store(exc_limit_ >= 0);
-        // at least 64 KiB of text per thread
-        parts_ = static_cast<int>(
-            std::min<size_t>(nthreads_, std::max<size_t>(1, PackBlocks(job->size) / 256)));
-        pending_ = parts_ - 1;
-        ++generation_;
-      }
-      const double t0 = GetTime();
-      if (parts_ > 1) cv_part_.notify_all();
-      int result = PackJob::kRejected;
-      std::exception_ptr err;
-      try {
-        DMLC_FAULT_POINT("pack");
-        if (fits_.load()) PackPart(job, 0);
-      } catch (...) {
-        err = std::current_exception();
-      }
-      {
-        std::unique_lock<std::mutex> lk(mu_);
-        cv_lead_.wait(lk, [&] { return pending_ == 0; });
-        if (!err && part_error_) err = part_error_;
-        part_error_ = nullptr;
-      }
-      if (!err && fits_.load()) {
-        try {
-          std::vector<uint32_t>& all = exc_[0];
-          for (int p = 1; p < parts_; ++p) all.insert(all.end(), exc_[p].begin(), exc_[p].end());
-          if (static_cast<long>(all.size()) <= exc_limit_) {
-            job->packed_bytes = PackFinish(reinterpret_cast<const uint8_t*>(job->ptr), job->size,
-                                           alphabet_, all, job->out);
-            job->nexc = static_cast<uint32_t>(all.size());
-            result = PackJob::kPacked;
+        for (;;) {
+          if (stop_) return;
+          if ((o = ClaimLocked(&r)) != nullptr) break;
+          if (OpenLocked()) {
+            cv_work_.notify_all();
+            continue;
           }
+          cv_work_.wait(lk);
+        }
+      }
+      // range after range of this job; the next one is claimed before this
+      // one is reported, so the job stays open in between
+      while (o != nullptr) {
+        const size_t nranges = o->nranges;  // (of this phase: read while a range is held)
+        try {
+          RunRange(o, r);
         } catch (...) {
-          err = std::current_exception();
+          o->fits.store(false);
+          std::lock_guard<std::mutex> lk(mu_);
+          if (!o->err) o->err = std::current_exception();
+        }
+        const size_t next = o->next.fetch_add(1);
+        if (o->done.fetch_add(1) + 1 == nranges) {
+          if (!o->copying && FinishPack(o)) {
+            r = 0;
+          } else {
+            Settle(o);
+            o = nullptr;
+          }
+        } else if (next < nranges) {
+          r = next;
+        } else {
+          o = nullptr;
         }
       }
-      pack_sec_.store(pack_sec_.load(std::memory_order_relaxed) + (GetTime() - t0),
-                      std::memory_order_relaxed);
-      {
-        std::lock_guard<std::mutex> lk(mu_);
-        if (err) {
-          error_ = err;
-          result = PackJob::kFailed;
-        }
-        job->state.store(result);
-        current_ = nullptr;
-      }
-      cv_done_.notify_all();
-    }
-  }
-  /*! \brief threads 1..: pack their part of the leader's current job */
-  void Help(int t) {
-    size_t seen = 0;
-    for (;;) {
-      PackJob* job = nullptr;
-      {
-        std::unique_lock<std::mutex> lk(mu_);
-        cv_part_.wait(lk, [&] { return stop_ || generation_ != seen; });
-        if (stop_) return;
-        seen = generation_;
-        if (t >= parts_) continue;
-        job = current_;
-      }
-      std::exception_ptr err;
-      try {
-        PackPart(job, t);
-      } catch (...) {
-        err = std::current_exception();
-      }
-      {
-        std::lock_guard<std::mutex> lk(mu_);
-        if (err && !part_error_) part_error_ = err;
-        --pending_;
-      }
-      cv_lead_.notify_one();
     }
   }
 
   const int nthreads_;
-  const size_t distance_;
+  std::atomic<size_t> distance_;
+  const size_t range_blocks_;
+  const PackEncoder encoder_;
   uint8_t alphabet_[16];
   std::mutex mu_;
-  std::condition_variable cv_work_, cv_part_, cv_lead_, cv_done_;
+  std::condition_variable cv_work_, cv_done_;
   std::deque<PackJob*> queue_;
-  PackJob* current_{nullptr};
-  size_t generation_{0};
-  int parts_{1}, pending_{0};
-  long exc_limit_{0};
-  std::atomic<long> exc_total_{0};
-  std::atomic<bool> fits_{true};
+  Open open_[kOpenJobs];
+  int nopen_{0};
+  size_t opened_{0};
+  double open_since_{0};
   std::atomic<size_t> submitted_{0};
   std::atomic<double> pack_sec_{0};
-  std::vector<std::vector<uint32_t>> exc_;
-  std::exception_ptr error_, part_error_;
+  std::exception_ptr error_;
   bool stop_{false};
   std::vector<std::thread> workers_;
 };

@@ -26,17 +26,6 @@ namespace {
 constexpr uint8_t kBad = 0x80;
 constexpr size_t kBlockNibbles = kPackBlockBytes / 2;
 
-/*! \brief byte -> code, kBad outside the alphabet (symbols >= 0x80 never encode) */
-struct EncodeTable {
-  uint8_t enc[256];
-  explicit EncodeTable(const uint8_t alphabet[16]) {
-    std::memset(enc, kBad, sizeof(enc));
-    for (int c = 15; c >= 0; --c) {
-      if (alphabet[c] < 0x80) enc[alphabet[c]] = static_cast<uint8_t>(c);
-    }
-  }
-};
-
 /*! \brief codes of src[0, len) into out[0, (len+1)/2); false: a byte outside the alphabet */
 bool BlockScalar(const uint8_t* src, size_t len, const uint8_t* enc, uint8_t* out) {
   uint8_t bad = 0;
@@ -149,6 +138,13 @@ PackIsa Resolve(PackIsa isa) {
 
 }  // namespace
 
+PackEncoder::PackEncoder(const uint8_t alphabet[16]) {
+  std::memset(enc, kBad, sizeof(enc));
+  for (int c = 15; c >= 0; --c) {
+    if (alphabet[c] < 0x80) enc[alphabet[c]] = static_cast<uint8_t>(c);
+  }
+}
+
 bool PackIsaSupported(PackIsa isa) {
   switch (isa) {
     case PackIsa::kAuto:
@@ -186,9 +182,8 @@ long PackMaxExceptions(size_t n, double ratio) {
 }
 
 bool PackRange(const uint8_t* text, size_t n, size_t block_begin, size_t block_end,
-               const uint8_t alphabet[16], uint8_t* nibbles, std::vector<uint32_t>* exc,
+               const PackEncoder& table, uint8_t* nibbles, std::vector<uint32_t>* exc,
                std::atomic<long>* exc_total, long exc_limit, PackIsa isa) {
-  const EncodeTable table(alphabet);
   const PackIsa use = Resolve(isa);
   (void)use;
   long own = 0;
@@ -224,8 +219,15 @@ bool PackRange(const uint8_t* text, size_t n, size_t block_begin, size_t block_e
   return fits;
 }
 
-size_t PackFinish(const uint8_t* text, size_t n, const uint8_t alphabet[16],
-                  const std::vector<uint32_t>& exc, uint8_t* packed) {
+bool PackRange(const uint8_t* text, size_t n, size_t block_begin, size_t block_end,
+               const uint8_t alphabet[16], uint8_t* nibbles, std::vector<uint32_t>* exc,
+               std::atomic<long>* exc_total, long exc_limit, PackIsa isa) {
+  return PackRange(text, n, block_begin, block_end, PackEncoder(alphabet), nibbles, exc, exc_total,
+                   exc_limit, isa);
+}
+
+size_t PackFinishHeader(size_t n, const uint8_t alphabet[16], const std::vector<uint32_t>& exc,
+                        uint8_t* packed) {
   PackedHeader h;
   h.n = n;
   h.nexc = static_cast<uint32_t>(exc.size());
@@ -239,14 +241,26 @@ size_t PackFinish(const uint8_t* text, size_t n, const uint8_t alphabet[16],
   const size_t idx_bytes = (exc.size() * 4 + 15) & ~size_t(15);
   std::memset(idx, 0, idx_bytes);
   if (!exc.empty()) std::memcpy(idx, exc.data(), exc.size() * 4);
-  uint8_t* raw = idx + idx_bytes;
-  for (size_t i = 0; i < exc.size(); ++i) {
+  return PackedBytes(n, exc.size());
+}
+
+void PackCopyExceptions(const uint8_t* text, size_t n, const std::vector<uint32_t>& exc,
+                        size_t first, size_t last, uint8_t* packed) {
+  uint8_t* raw = packed + sizeof(PackedHeader) + NibbleAreaBytes(n) +
+                 ((exc.size() * 4 + 15) & ~size_t(15));
+  for (size_t i = first; i < last; ++i) {
     const size_t off = static_cast<size_t>(exc[i]) * kPackBlockBytes;
     const size_t len = std::min(kPackBlockBytes, n - off);
     std::memcpy(raw + i * kPackBlockBytes, text + off, len);
     std::memset(raw + i * kPackBlockBytes + len, 0, kPackBlockBytes - len);
   }
-  return PackedBytes(n, exc.size());
+}
+
+size_t PackFinish(const uint8_t* text, size_t n, const uint8_t alphabet[16],
+                  const std::vector<uint32_t>& exc, uint8_t* packed) {
+  const size_t size = PackFinishHeader(n, alphabet, exc, packed);
+  PackCopyExceptions(text, n, exc, 0, exc.size(), packed);
+  return size;
 }
 
 bool PackText(const uint8_t* text, size_t n, const uint8_t alphabet[16], double ratio,

@@ -60,6 +60,13 @@ inline size_t PackedBytes(size_t n, size_t nexc) {
  *  fits.  A negative ratio lifts the bound (every chunk packs; the tests) */
 long PackMaxExceptions(size_t n, double ratio = kPackMaxRatio);
 
+/*! \brief byte -> code table of an alphabet, 0x80 outside it (symbols >= 0x80
+ *  never encode); built once by a caller that packs many ranges */
+struct PackEncoder {
+  uint8_t enc[256];
+  explicit PackEncoder(const uint8_t alphabet[16]);
+};
+
 /*!
  * \brief pack blocks [block_begin, block_end) of text[0, n): nibbles go to
  *  their fixed position in `nibbles` (the chunk's nibble area), the indices of
@@ -68,8 +75,21 @@ long PackMaxExceptions(size_t n, double ratio = kPackMaxRatio);
  * \param exc_limit stop, returning false, once more than this many were counted
  */
 bool PackRange(const uint8_t* text, size_t n, size_t block_begin, size_t block_end,
+               const PackEncoder& encoder, uint8_t* nibbles, std::vector<uint32_t>* exc,
+               std::atomic<long>* exc_total, long exc_limit, PackIsa isa = PackIsa::kAuto);
+/*! \brief the same, building the alphabet's table for this call */
+bool PackRange(const uint8_t* text, size_t n, size_t block_begin, size_t block_end,
                const uint8_t alphabet[16], uint8_t* nibbles, std::vector<uint32_t>* exc,
                std::atomic<long>* exc_total, long exc_limit, PackIsa isa = PackIsa::kAuto);
+
+/*! \brief the parts of PackFinish, for a caller that shares the copy of the
+ *  exception blocks among threads: the header, the nibble area's zero tail and
+ *  the exception indices (returns the packed size), then the raw bytes of
+ *  exception blocks [first, last) of `exc` */
+size_t PackFinishHeader(size_t n, const uint8_t alphabet[16], const std::vector<uint32_t>& exc,
+                        uint8_t* packed);
+void PackCopyExceptions(const uint8_t* text, size_t n, const std::vector<uint32_t>& exc,
+                        size_t first, size_t last, uint8_t* packed);
 
 /*! \brief write the header, the nibble area's zero tail and the exception
  *  lists around an already packed nibble area; returns the packed size */

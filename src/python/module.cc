@@ -480,6 +480,7 @@ class PyDeviceParser {
     d["exception_blocks"] = s.exception_blocks;
     d["pack_sec"] = s.pack_sec;
     d["wait_pack_sec"] = s.wait_pack_sec;
+    d["wait_pack_idle_sec"] = s.wait_pack_idle_sec;
     d["unpack_staging_bytes"] = s.unpack_staging_bytes;
     return d;
   }
