@@ -160,7 +160,7 @@ class HashedFM(torch.nn.Module):
     :func:`~dmlc_core_amd.ops.hashed_dense`, with its quantisation ``scale``.
     ``y = b + x.w + 1/2 sum_f ((x V)_f^2 - (x^2 V^2)_f)``; the last term is
     ``x^2 . q`` with ``q = rowsum(V^2)``.  On a GPU (rank 16, dim a multiple of
-    128) forward and backward are the bf16-MFMA kernels of
+    128 from 128 to 2048) forward and backward are the bf16-MFMA kernels of
     ``src/gpu/fm_kernels.hip``, each reading the fp8 batch once; elsewhere the
     fp32 formula runs on the dequantised batch (``self.gemm`` tells which).
     """

@@ -91,7 +91,12 @@ def _stream() -> int:
 
 def spmv(csr: Dict, w: torch.Tensor, bias: float = 0.0) -> torch.Tensor:
     """y[r] = sum_j value[j] * w[index[j]] + bias  (K11, 16 lanes per row).
-    Takes contiguous arrays or a transpose's interleaved (index, value) pairs."""
+    Takes contiguous arrays or a transpose's interleaved (index, value) pairs.
+    Rows of any length (empty rows give ``bias``), any number of rows (none
+    gives an empty result), 32- or 64-bit indices, ``value`` optional (1.0);
+    ``offset`` may be a slice of a larger CSR's row pointer (``offset[0] !=
+    0``) next to the whole ``index`` / ``value``.  Sums are f32, in no fixed
+    order."""
     _check(csr, pairs=True)
     assert w.dtype == torch.float32 and w.is_cuda and w.is_contiguous()
     nrows = csr["offset"].numel() - 1
@@ -103,7 +108,9 @@ def spmv(csr: Dict, w: torch.Tensor, bias: float = 0.0) -> torch.Tensor:
 
 def spmv_t(csr: Dict, d: torch.Tensor, num_features: int) -> torch.Tensor:
     """g[index[j]] += value[j] * d[row(j)]  (transposed K11, f32 atomics).
-    A transpose's pair views are unpaired into contiguous copies first."""
+    A transpose's pair views are unpaired into contiguous copies first.
+    Takes the same CSR shapes as :func:`spmv`; rows whose ``d`` is +-0 are
+    skipped (they add nothing), and a CSR of no rows gives zeros."""
     csr = _unpair(csr)
     _check(csr)
     assert d.dtype == torch.float32 and d.is_cuda and d.is_contiguous()
@@ -119,7 +126,19 @@ def hashed_dense(csr: Dict, dim: int, seed: int = 0, fp8: bool = True,
     """K9: signed feature hashing of every row into ``dim`` buckets.
 
     Returns float8_e4m3fn [rows, dim] (gfx950 OCP fp8, hardware conversion)
-    when ``fp8`` else float32.  LibFM fields are folded into the hash key.
+    when ``fp8`` else float32.  LibFM fields are folded into the hash key
+    (``index ^ field << 40``, so field 0 is the same key as no field); a
+    missing ``value`` counts 1.0 per entry.  ``dim``: a multiple of 4 from 4
+    to 8192, anything else raises.
+
+    fp8: each bucket's f32 sum times ``scale`` (one f32 product) is rounded
+    to nearest, ties to even, subnormals included -- for ``|x| <= 464`` byte
+    for byte torch's ``float32 -> float8_e4m3fn`` cast (464 still gives 448).
+    Out of range, as produced by gfx950's conversion: a finite ``|x| > 464``
+    and ``+-inf`` give the NaN code with the value's sign (0x7F / 0xFF; no
+    saturation to 448; torch's cast gives the same bytes), and a NaN gives
+    0xFF whatever its sign (torch's cast gives 0x7F for a positive NaN).
+    Choose ``scale`` so that the sums stay within +-448.
     """
     csr = _unpair(csr)
     _check(csr)

@@ -29,8 +29,31 @@
     }                                                                           \
   } while (0)
 
+/*! \brief throw dmlc::Error if the kernel launch just made was rejected (a
+ *  launch returns nothing; the runtime keeps its error for this call) */
+#define DMLC_HIP_CHECK_LAUNCH() DMLC_HIP_CHECK(hipGetLastError())
+
 namespace dmlc {
 namespace gpu {
+
+/*! \brief dynamic LDS (bytes) a launch may ask for without opting in */
+constexpr size_t kDefaultDynamicLdsBytes = 64 * 1024;
+/*!
+ * \brief call before launching `kernel` with `bytes` of dynamic LDS and
+ *  follow the launch with DMLC_HIP_CHECK_LAUNCH(): above 64 KiB the kernel is
+ *  opted in to that much, and an earlier call's pending error is dropped so
+ *  that the check reports this launch alone.  A size the device cannot give
+ *  throws here or at the check; the caller never reads unwritten output.
+ */
+template <typename Kernel>
+inline void PrepareLdsLaunch(Kernel kernel, size_t bytes) {
+  if (bytes > kDefaultDynamicLdsBytes) {
+    DMLC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       static_cast<int>(bytes)));
+  }
+  (void)hipGetLastError();
+}
 
 /*! \brief number of visible HIP devices (0 when no GPU / no driver) */
 int DeviceCount();

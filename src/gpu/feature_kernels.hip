@@ -12,6 +12,7 @@
  * K9 accumulates one row per wave in LDS (ds_add_f32) and converts pairs of
  * f32 to fp8 with the gfx950 v_cvt_pk_fp8_f32 instruction.
  */
+#include <dmlc/gpu/hip_utils.h>
 #include <dmlc/logging.h>
 #include <hip/hip_runtime.h>
 
@@ -261,9 +262,11 @@ void LaunchHashedDenseFP8(const uint64_t* offset, const IndexType* index, const 
                           uint32_t seed, uint8_t* out, hipStream_t stream) {
   if (nrows == 0) return;
   const size_t lds = static_cast<size_t>(dim) * sizeof(float) * (kThreads / dev::kWave);
+  PrepareLdsLaunch(k_hashed_dense<IndexType, true>, lds);
   hipLaunchKernelGGL((k_hashed_dense<IndexType, true>), dim3(GridFor(nrows, kThreads / dev::kWave)),
                      dim3(kThreads), lds, stream, offset, index, value, field, nrows, dim, scale,
                      seed, static_cast<void*>(out));
+  DMLC_HIP_CHECK_LAUNCH();
 }
 
 template <typename IndexType>
@@ -272,9 +275,11 @@ void LaunchHashedDenseF32(const uint64_t* offset, const IndexType* index, const 
                           float* out, hipStream_t stream) {
   if (nrows == 0) return;
   const size_t lds = static_cast<size_t>(dim) * sizeof(float) * (kThreads / dev::kWave);
+  PrepareLdsLaunch(k_hashed_dense<IndexType, false>, lds);
   hipLaunchKernelGGL((k_hashed_dense<IndexType, false>),
                      dim3(GridFor(nrows, kThreads / dev::kWave)), dim3(kThreads), lds, stream,
                      offset, index, value, field, nrows, dim, 1.0f, seed, static_cast<void*>(out));
+  DMLC_HIP_CHECK_LAUNCH();
 }
 
 #define DMLC_INSTANTIATE_FEATURE(I)                                                           \

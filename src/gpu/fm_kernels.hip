@@ -28,6 +28,7 @@
  * F3 k_fm_reduce + F4 k_fm_grads: the partials summed in a fixed order and
  *   turned into dw, dV on the device (no torch reduction over the partials).
  */
+#include <dmlc/gpu/hip_utils.h>
 #include <dmlc/logging.h>
 #include <hip/hip_runtime.h>
 
@@ -800,8 +801,10 @@ void LaunchFmForward(const uint8_t* x, int64_t rows, int dim, const void* wt_bf1
   const int64_t want = (ntiles + kFwdThreads / kWave - 1) / (kFwdThreads / kWave);
   const int64_t cap = static_cast<int64_t>(num_cus) * 4;  // persistent: LDS [w | V] loaded once per CU slot
   const int grid = static_cast<int>(want < cap ? want : cap);
+  PrepareLdsLaunch(k_fm_fwd, FmForwardSharedBytes(dim));
   hipLaunchKernelGGL(k_fm_fwd, dim3(grid), dim3(kFwdThreads), FmForwardSharedBytes(dim), stream, x,
                      rows, dim, reinterpret_cast<const __bf16*>(wt_bf16), q, bias, sx, y, xv);
+  DMLC_HIP_CHECK_LAUNCH();
 }
 
 

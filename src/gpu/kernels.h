@@ -217,7 +217,8 @@ size_t LaunchTileFill(const char* text, size_t nbytes, TextFormat format,
  *  lines that start in it (followed past the tile end, any length).  Sets
  *  kFlagIrregular for tokens only the exact kernels parse (qid:, junk; re-run
  *  the chunk with LaunchTextHashed), merges kFlagNegIndex.  dim: multiple of
- *  16, <= 4096.
+ *  16, 16 .. 4096 (16 x dim bytes of dynamic LDS next to ~20 KiB of static
+ *  staging; checked launch as for K9; the same fp8 conversion).
  */
 /*!
  *  One pass (one_pass != nullptr; tile_prefix / nlines unused): no C1 / C2 --
@@ -355,7 +356,16 @@ void LaunchRecordIOGather(const uint8_t* src, const uint64_t* src_off, const uin
 /*!
  * \brief K9: hashed dense batch in OCP fp8 e4m3: out[r, h(index) % dim] +=
  *  value * scale, accumulated in f32 in LDS and converted with gfx950
- *  v_cvt_pk_fp8_f32.  rows = nrows, dim <= 8192.
+ *  v_cvt_pk_fp8_f32.  rows = nrows; dim: multiple of 4, 4 .. 8192 (16 x dim
+ *  bytes of dynamic LDS per workgroup, up to 128 KiB: the launch opts in to
+ *  it and is checked, a refused launch throws).  A wave takes rows r, r +
+ *  4 x grid, ...: its LDS row is zeroed again by each readout.
+ *  Conversion: round to nearest even of sum * scale (f32), subnormals
+ *  included; |x| <= 464 gives a finite code (464 -> 448).  Out of range, as
+ *  produced by gfx950's conversion: finite |x| > 464 and +-inf give the NaN
+ *  code with the value's sign (0x7F / 0xFF, no saturation; the same bytes as
+ *  torch's float8_e4m3fn cast), a NaN gives 0xFF whatever its sign (torch:
+ *  0x7F for a positive NaN).
  */
 template <typename IndexType>
 void LaunchHashedDenseFP8(const uint64_t* offset, const IndexType* index, const float* value,
@@ -372,7 +382,9 @@ void LaunchHashedDenseF32(const uint64_t* offset, const IndexType* index, const 
  *  [rows x dim] batch -- OCP fp8 e4m3 (x scale) or f32 -- with features
  *  hashed exactly as LaunchHashedDense* does, plus its label; no CSR is
  *  written.  line_starts / line_info as for LaunchTextFill (K1, K2 + K3).
- *  dim: multiple of 4, <= 4096 (LDS row per wave).  Merges kFlagNegIndex.
+ *  dim: multiple of 4, 4 .. 4096 (LDS row per wave, 16 x dim bytes of dynamic
+ *  LDS; checked launch as for K9; the same fp8 conversion).  Merges
+ *  kFlagNegIndex.
  */
 template <typename IndexType>
 void LaunchTextHashed(const char* text, size_t nbytes, const uint32_t* line_starts, size_t nlines,
@@ -397,7 +409,9 @@ size_t FmForwardSharedBytes(int dim);
 /*!
  * \brief F1: y[r] = bias + sx x_r.w + 1/2 (|sx x_r V|^2 - sx^2 x_r^2.q) and
  *  xv[r] = sx x_r V for the fp8 e4m3 batch x [rows x dim]; wt_bf16 = [w | V]^T
- *  as bf16 [17 x dim], q[n] = sum_f V_nf^2.  dim: multiple of 128, <= 2048.
+ *  as bf16 [17 x dim], q[n] = sum_f V_nf^2.  dim: multiple of 128, 128 .. 2048
+ *  (FmForwardSharedBytes: 38 dim + 272 bytes of dynamic LDS, above 64 KiB
+ *  from dim 1792; the launch opts in to it and is checked).
  */
 void LaunchFmForward(const uint8_t* x, int64_t rows, int dim, const void* wt_bf16, const float* q,
                      const float* bias, float sx, float* y, float* xv, int num_cus,
@@ -405,7 +419,9 @@ void LaunchFmForward(const uint8_t* x, int64_t rows, int dim, const void* wt_bf1
 /*!
  * \brief F2: per-block partials part[nblocks][18][dim] of Z = G^T x (G_r =
  *  [g_r, g_r xv_r], rows 0..16) and t = (x^2)^T g (row 17); the caller sums
- *  over blocks.  dim: multiple of 128.
+ *  over blocks.  dim: multiple of 128 (any number of 1024-feature slabs;
+ *  waves past dim in the last slab only stage G); nblocks may exceed the
+ *  32-row tiles (workgroups without rows write zeros).
  */
 void LaunchFmBackward(const uint8_t* x, int64_t rows, int dim, const float* g, const float* xv,
                       int nblocks, float* part, hipStream_t stream);

@@ -22,6 +22,7 @@
  *  - Number parsing is the shared host/device code of src/data/strtonum.h,
  *    so the device CSR is bit-identical to the CPU parsers' output.
  */
+#include <dmlc/gpu/hip_utils.h>
 #include <hip/hip_runtime.h>
 
 #include "../data/strtonum.h"
@@ -880,9 +881,11 @@ void LaunchTextHashed(const char* text, size_t nbytes, const uint32_t* line_star
   const dim3 grid(LineGrid(nlines)), block(kThreads);
   const size_t smem = static_cast<size_t>(kWavesPerBlock) * dim * sizeof(float);
 #define DMLC_HASH_LAUNCH(FMT, FP8)                                                              \
+  PrepareLdsLaunch(k_text_hash<FMT, IndexType, FP8>, smem);                                     \
   hipLaunchKernelGGL((k_text_hash<FMT, IndexType, FP8>), grid, block, smem, stream, t, nbytes, \
                      line_starts, nlines, line_info, row_base, dim, scale, seed, out, labels,    \
-                     partials)
+                     partials);                                                                  \
+  DMLC_HIP_CHECK_LAUNCH()
   if (format == TextFormat::kLibFM) {
     if (fp8) {
       DMLC_HASH_LAUNCH(TextFormat::kLibFM, true);

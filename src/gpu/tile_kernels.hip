@@ -2067,8 +2067,10 @@ size_t LaunchTileHashed(const char* text, size_t nbytes, TextFormat format,
   if (ntiles != 0) {
     const dim3 grid(static_cast<unsigned>(groups));
 #define DMLC_TILE_HASH(FMT, FP8, ONE)                                                          \
+  PrepareLdsLaunch(k_tile_hash<FMT, IndexType, FP8, ONE>, smem);                                \
   hipLaunchKernelGGL((k_tile_hash<FMT, IndexType, FP8, ONE>), grid, dim3(kThreads), smem, stream, \
-                     t, nbytes, ntiles, tile_prefix, tgt, partials)
+                     t, nbytes, ntiles, tile_prefix, tgt, partials);                            \
+  DMLC_HIP_CHECK_LAUNCH()
 #define DMLC_TILE_HASH_FMT(FMT)             \
   if (one_pass != nullptr) {                \
     if (fp8) {                              \

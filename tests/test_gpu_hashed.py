@@ -16,40 +16,9 @@ import torch
 
 from dmlc_core_amd import data, ops
 from dmlc_core_amd.models import HashedFM
+from pyref import ref_dense, ref_hash  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-M64 = (1 << 64) - 1
-
-
-def ref_hash(keys: np.ndarray, seed: int) -> np.ndarray:
-    x = [int(k) for k in keys]
-    out = np.empty(len(x), dtype=np.uint64)
-    s = (seed * 0x9E3779B97F4A7C15) & M64
-    for i, v in enumerate(x):
-        v ^= s
-        v = ((v ^ (v >> 33)) * 0xFF51AFD7ED558CCD) & M64
-        v = ((v ^ (v >> 33)) * 0xC4CEB9FE1A85EC53) & M64
-        v ^= v >> 33
-        out[i] = v & 0xFFFFFFFF
-    return out
-
-
-def ref_dense(host, dim, seed, libfm):
-    rows = len(host["label"])
-    off = host["offset"].astype(np.int64)
-    idx = host["index"].astype(np.uint64)
-    val = (host["value"].astype(np.float64) if host.get("value") is not None
-           else np.ones(len(idx)))
-    keys = idx ^ (host["field"].astype(np.uint64) << np.uint64(40)) if libfm else idx
-    h = ref_hash(keys, seed)
-    bucket = (h % np.uint64(dim)).astype(np.int64)
-    sign = np.where(h & np.uint64(0x80000000), -1.0, 1.0)
-    rowid = np.repeat(np.arange(rows), np.diff(off))
-    out = np.zeros((rows, dim), dtype=np.float64)
-    np.add.at(out, (rowid, bucket), sign * val)
-    share = np.zeros((rows, dim), dtype=np.int64)
-    np.add.at(share, (rowid, bucket), 1)
-    return out, share
 
 
 @pytest.fixture(scope="module", params=["libfm", "libsvm"])
