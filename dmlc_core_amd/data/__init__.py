@@ -15,7 +15,7 @@ from .. import _dmlc
 
 __all__ = ["Parser", "RowBlockIter", "GPUParser", "ShuffledGPUParser", "DeviceCSR", "csr_to_torch",
            "iter_blocks", "write_synthetic", "to_sparse_csr", "GPUBlockDataset", "PageCache",
-           "write_page_cache"]
+           "write_page_cache", "RowBatches", "row_order"]
 
 write_synthetic = _dmlc.write_synthetic
 # packed H2D (src/gpu/text_pack.h): the host packer, its CPU reference unpack
@@ -311,3 +311,126 @@ class GPUBlockDataset:
                 p.before_first()
             while p.next():
                 yield p.value_torch()
+
+
+def row_order(n_rows: int, seed: int, epoch: int):
+    """The row permutation of one epoch of :class:`RowBatches`: a pure
+    function of its arguments, drawn on the CPU so that it is the same on
+    every machine -- ``torch.randperm(n_rows)`` under a CPU
+    ``torch.Generator`` seeded with ``(seed * 1000003 + epoch) mod 2**32``
+    (the CPU generator keeps 32 bits of a seed); an int64 tensor on the host."""
+    import torch
+
+    if n_rows < 0 or epoch < 0:
+        raise ValueError("n_rows and epoch must be >= 0")
+    g = torch.Generator(device="cpu")
+    g.manual_seed((int(seed) * 1000003 + int(epoch)) % (1 << 32))
+    return torch.randperm(int(n_rows), generator=g, dtype=torch.int64)
+
+
+class RowBatches:
+    """One epoch of row-shuffled minibatches of a CSR resident in HBM.
+
+    ``csr_dict``: a ``csr_to_torch`` dict (or a row slice of one); its
+    ``label`` / ``weight`` / ``qid`` tensors travel with the rows.  Each item
+    is the :func:`dmlc_core_amd.ops.gather_rows` result for the next
+    ``batch_rows`` rows of the epoch's order -- ``row_order(n_rows, seed,
+    epoch)``, or file order with ``shuffle=False`` (through the same gather).
+    :meth:`set_epoch` picks the epoch (and rewinds); iterating again without
+    it repeats the same order.  ``drop_last`` drops a short last batch.
+
+    The items are gathered into ``buffers`` rotating sets of device buffers:
+    an item stays valid until ``buffers - 1`` further items have been
+    requested (with the default 2: until the item after the next one), then
+    its tensors are overwritten -- consume or clone it before that.
+
+    ``state_dict`` / ``load_state_dict`` carry ``(seed, epoch, next_batch,
+    batch_rows, n_rows)``: a loaded iterator continues with batch
+    ``next_batch`` of that epoch.  ``len()`` is the batches per epoch.
+    """
+
+    def __init__(self, csr_dict: Dict, batch_rows: int, shuffle: bool = True, seed: int = 0,
+                 drop_last: bool = False, buffers: int = 2):
+        if batch_rows < 1:
+            raise ValueError("batch_rows must be >= 1")
+        if buffers < 1:
+            raise ValueError("buffers must be >= 1")
+        self.csr = csr_dict
+        self.n_rows = int(csr_dict["offset"].numel()) - 1
+        self.batch_rows, self.shuffle, self.seed = int(batch_rows), bool(shuffle), int(seed)
+        self.drop_last, self.buffers = bool(drop_last), int(buffers)
+        self.epoch, self._next = 0, 0
+        self._out = [None] * self.buffers
+        self._order = None  # (epoch, device tensor)
+
+    def __len__(self) -> int:
+        if self.drop_last:
+            return self.n_rows // self.batch_rows
+        return (self.n_rows + self.batch_rows - 1) // self.batch_rows
+
+    def set_epoch(self, epoch: int) -> None:
+        """Choose the epoch whose order the next iteration follows, from its
+        first batch."""
+        if epoch < 0:
+            raise ValueError("epoch must be >= 0")
+        self.epoch, self._next = int(epoch), 0
+
+    def batch_bounds(self, k: int):
+        """positions ``[b, e)`` of batch ``k`` in the epoch's order"""
+        if not 0 <= k < len(self):
+            raise IndexError(f"batch {k} of {len(self)}")
+        b = k * self.batch_rows
+        return b, min(self.n_rows, b + self.batch_rows)
+
+    def state_dict(self) -> Dict:
+        """Checkpointable position (store it next to the model state)."""
+        return {"seed": self.seed, "epoch": self.epoch, "next_batch": self._next,
+                "batch_rows": self.batch_rows, "n_rows": self.n_rows}
+
+    def load_state_dict(self, state: Dict) -> None:
+        for k in ("seed", "batch_rows", "n_rows"):
+            if state[k] != getattr(self, k):
+                raise ValueError(f"state is for {k}={state[k]!r}, iterator has {getattr(self, k)!r}")
+        nb = int(state["next_batch"])
+        if not 0 <= nb <= len(self):
+            raise ValueError(f"state is for next_batch={nb}, iterator has {len(self)} batches")
+        self.epoch, self._next = int(state["epoch"]), nb
+
+    def _device_order(self):
+        import torch
+
+        if self._order is None or self._order[0] != (self.epoch, self.shuffle):
+            dev = self.csr["index"].device
+            if self.shuffle:
+                order = row_order(self.n_rows, self.seed, self.epoch).to(dev)
+            else:
+                order = torch.arange(self.n_rows, dtype=torch.int64, device=dev)
+            self._order = ((self.epoch, self.shuffle), order)
+        return self._order[1]
+
+    def _gather(self, rows, slot: int) -> Dict:
+        from .. import ops
+
+        out = self._out[slot]
+        if out is None or out["_buffers"]["offset"].numel() < rows.numel() + 2:
+            # the slot's first batch (or the first after a short last batch
+            # sized them) allocates its buffers
+            return ops.gather_rows(self.csr, rows)
+        try:
+            return ops.gather_rows(self.csr, rows, out=self._out[slot])
+        except ops._GatherOutTooSmall as e:
+            # a batch with more entries than any before it in this slot (nothing
+            # was written past the buffers): new buffers with room to spare
+            grown = ops.gather_buffers(self.csr, self.batch_rows, e.nnz + e.nnz // 4)
+            return ops.gather_rows(self.csr, rows, out=grown)
+
+    def __iter__(self):
+        order = self._device_order() if len(self) > self._next else None
+        while self._next < len(self):
+            k = self._next
+            b, e = self.batch_bounds(k)
+            item = self._gather(order[b:e], k % self.buffers)
+            self._out[k % self.buffers] = item
+            self._next = k + 1
+            yield item
+        self._next = 0

@@ -17,7 +17,7 @@ import torch
 from .. import _dmlc
 
 __all__ = ["spmv", "spmv_t", "hashed_dense", "SpMVFunction", "csr_spmv", "transpose",
-           "release_workspace"]
+           "gather_rows", "gather_buffers", "release_workspace"]
 
 # persistent transpose scratch per (device, stream), grow-only: a rebuild (a
 # further shard, a refreshed batch) allocates no multi-GB scratch again
@@ -35,8 +35,8 @@ def _workspace(nbytes: int, dev) -> torch.Tensor:
 
 
 def release_workspace() -> None:
-    """Free the persistent scratch of :func:`transpose` (it is kept between
-    calls so that later builds allocate only their outputs)."""
+    """Free the persistent scratch of :func:`transpose` and :func:`gather_rows`
+    (it is kept between calls so that later builds allocate only their outputs)."""
     _WORKSPACE.clear()
 
 
@@ -227,6 +227,171 @@ def transpose(csr: Dict, num_features: int, out: Optional[Dict] = None) -> Dict:
            "value": vals[:nnz] if vals is not None else None}
     if pairs is not None:
         res["pairs"] = pairs
+    return res
+
+
+_ROW_COLUMNS = (("label", 4), ("weight", 4), ("qid", 8))  # per-row columns and their item sizes
+_ERR_ROW, _ERR_CAPACITY, _ERR_SOURCE = 1, 2, 4  # kGatherErr* (src/gpu/kernels.h)
+
+
+class _GatherOutTooSmall(ValueError):
+    """``gather_rows(out=)``: the batch has ``nnz`` entries, the buffers fewer"""
+
+    def __init__(self, msg: str, nnz: int):
+        super().__init__(msg)
+        self.nnz = nnz
+
+
+def _gather_columns(csr: Dict, nrows: int) -> Dict:
+    """the per-row columns of ``csr`` that are tensors, checked"""
+    cols = {}
+    for k, size in _ROW_COLUMNS:
+        t = csr.get(k)
+        if not isinstance(t, torch.Tensor):
+            continue
+        if not t.is_cuda or not t.is_contiguous() or t.dim() != 1:
+            raise ValueError(f"csr[{k!r}] must be a contiguous device tensor")
+        if t.element_size() != size or (size == 4 and t.dtype != torch.float32):
+            raise ValueError(f"csr[{k!r}] must be {'float32' if size == 4 else '64-bit'}")
+        if t.numel() < nrows:
+            raise ValueError(f"csr[{k!r}] has {t.numel()} entries for {nrows} rows")
+        cols[k] = t
+    return cols
+
+
+def gather_buffers(csr: Dict, max_rows: int, max_entries: int) -> Dict:
+    """Buffers for :func:`gather_rows`'s ``out=``: room for a selection of up
+    to ``max_rows`` rows with up to ``max_entries`` entries of ``csr`` (the
+    same columns and dtypes; nothing is gathered)."""
+    csr = _unpair(csr)
+    _check(csr)
+    dev = csr["index"].device
+    # one slot more than the row pointer needs: every result's ``offset`` is
+    # then a view of a larger buffer, which SpMVFunction's "auto" reads as a
+    # batch made per step (atomic gradient, no transpose per batch)
+    bufs = {"offset": torch.empty(max_rows + 2, dtype=torch.int64, device=dev),
+            "index": torch.empty(max_entries, dtype=csr["index"].dtype, device=dev)}
+    if csr.get("value") is not None:
+        bufs["value"] = torch.empty(max_entries, dtype=torch.float32, device=dev)
+    if csr.get("field") is not None:
+        bufs["field"] = torch.empty(max_entries, dtype=csr["field"].dtype, device=dev)
+    for k, t in _gather_columns(csr, 0).items():
+        bufs[k] = torch.empty(max_rows, dtype=t.dtype, device=dev)
+    return {"_buffers": bufs}
+
+
+def gather_rows(csr: Dict, rows: torch.Tensor, out: Optional[Dict] = None) -> Dict:
+    """Rows ``rows[0], rows[1], ...`` of a device CSR as a CSR batch (G1 / G2,
+    src/gpu/gather_kernels.hip): the ragged-row gather behind row-shuffled
+    minibatches of a resident shard.
+
+    ``csr``: a ``csr_to_torch`` / ``value_torch`` dict, a row-slice dict
+    (``offset[b:e + 1]`` next to the whole ``index`` / ``value``; row ids are
+    then relative to the slice) or a transpose (unpaired first).  ``rows``: a
+    1-D contiguous int64 or int32 device tensor of row ids, in any order,
+    duplicates allowed, possibly empty.
+
+    Returns ``offset`` int64 [n_sel + 1] from 0, ``index`` (the source's
+    dtype) and ``value`` (None if the source has none: no 1.0 is made up)
+    sliced to exactly nnz entries, ``field`` if the source dict has one, and
+    ``label`` / ``weight`` / ``qid`` for each that is a tensor in ``csr``.
+    The bytes are a pure function of the inputs (no atomics).  G1 writes each
+    selected row's length and per-row columns, the K3 scan turns the lengths
+    into the row pointer, and G2 copies the entries by output position: each
+    wave owns ``_dmlc.csr_gather_run_entries()`` consecutive output entries.
+
+    Runs on the current torch stream; the scan scratch is the persistent
+    workspace :func:`transpose` uses.  Exactly one device-to-host read per
+    call: one 16-byte copy holding the output nnz and the error word.  A row
+    id outside ``[0, nrows)`` raises ``ValueError`` (a negative id does not
+    count from the end).
+
+    ``out``: an earlier result (or :func:`gather_buffers`) whose buffers are
+    refilled in place; the full-capacity tensors travel under
+    ``out["_buffers"]`` and the result holds views of them, so buffers may be
+    larger than one batch needs.  ``offset`` needs n_sel + 1 slots, the per-row
+    columns n_sel, ``index`` / ``value`` / ``field`` nnz entries: ``ValueError``
+    if not.  G2 is bounded by the buffers' capacity, so nothing is written
+    past a short buffer before the error is raised; the earlier result's
+    contents are overwritten either way."""
+    csr = _unpair(csr)
+    _check(csr)
+    if not isinstance(rows, torch.Tensor) or not rows.is_cuda or not rows.is_contiguous() \
+            or rows.dim() != 1:
+        raise ValueError("rows must be a 1-D contiguous device tensor")
+    if rows.dtype not in (torch.int64, torch.int32):
+        raise ValueError(f"rows must be int64 or int32, got {rows.dtype}")
+    offset, index, value, field = csr["offset"], csr["index"], csr.get("value"), csr.get("field")
+    if offset.element_size() != 8 or offset.numel() < 1:
+        raise ValueError("csr['offset'] must be a 64-bit row pointer of rows + 1 entries")
+    if field is not None and (not field.is_cuda or not field.is_contiguous()
+                              or field.dtype != index.dtype):
+        raise ValueError("csr['field'] must be a contiguous device tensor of index's dtype")
+    nrows, n_sel, dev = offset.numel() - 1, rows.numel(), index.device
+    cols = _gather_columns(csr, nrows)
+    src_entries = min(t.numel() for t in (index, value, field) if t is not None)
+    entry_keys = ["index"] + (["value"] if value is not None else []) \
+        + (["field"] if field is not None else [])
+    if out is None:
+        bufs = {"offset": torch.empty(n_sel + 2, dtype=torch.int64, device=dev)}  # gather_buffers
+        for k, t in cols.items():
+            bufs[k] = torch.empty(n_sel, dtype=t.dtype, device=dev)
+    else:
+        bufs = out.get("_buffers")
+        if bufs is None:
+            bufs = {k: out[k] for k in ["offset"] + entry_keys + list(cols) if out.get(k) is not None}
+        for k in ["offset"] + entry_keys + list(cols):
+            t = bufs.get(k)
+            like = torch.int64 if k == "offset" else csr[k].dtype
+            if t is None or t.dtype != like or t.device != dev or not t.is_contiguous():
+                raise ValueError(f"gather_rows: out= has no {k!r} buffer of {like} on {dev}")
+            if k == "offset" and t.data_ptr() % 16:
+                raise ValueError("gather_rows: out= offset must be 16-byte aligned (the scan's loads)")
+            if k not in entry_keys and t.numel() < n_sel + (k == "offset"):
+                raise ValueError(f"gather_rows: out= does not fit this selection "
+                                 f"({k!r}: {t.numel()} slots for {n_sel} rows)")
+    status = torch.zeros(2, dtype=torch.int64, device=dev)  # [nnz, error word]
+    scratch = _workspace(8 * _dmlc.csr_gather_scratch_words(n_sel), dev)
+    rows64, stream = rows.dtype == torch.int64, _stream()
+    _dmlc.csr_gather_count(_ptr(offset), nrows, src_entries, _ptr(rows), rows64, n_sel,
+                           _ptr(cols.get("label")), _ptr(cols.get("weight")),
+                           _ptr(cols.get("qid")), _ptr(bufs["offset"]), _ptr(bufs.get("label")),
+                           _ptr(bufs.get("weight")), _ptr(bufs.get("qid")), _ptr(scratch),
+                           _ptr(status), _ptr(status) + 8, stream)
+
+    def fill(capacity: int) -> None:
+        _dmlc.csr_gather_fill(_ptr(offset), nrows, src_entries, _ptr(rows), rows64, n_sel,
+                              _ptr(bufs["offset"]), _ptr(status), _ptr(index), _ptr(value), _ptr(field),
+                              _ptr(bufs["index"]), _ptr(bufs.get("value")),
+                              _ptr(bufs.get("field")), capacity, _ptr(status) + 8, stream,
+                              _index64(csr))
+
+    if out is None:
+        # the read comes between G1 and G2, to size the outputs
+        nnz, err = status.tolist()
+        if not err:
+            for k in entry_keys:
+                bufs[k] = torch.empty(nnz, dtype=csr[k].dtype, device=dev)
+            fill(nnz)
+    else:
+        # G1, scan and G2 are queued back to back, G2 bounded by the buffers
+        capacity = min(bufs[k].numel() for k in entry_keys)
+        fill(capacity)
+        nnz, err = status.tolist()
+    if err & _ERR_ROW:
+        raise ValueError(f"gather_rows: a row id is outside [0, nrows) (nrows = {nrows})")
+    if err & _ERR_SOURCE:
+        raise ValueError("gather_rows: csr['offset'] descends or points past index / value / field")
+    if err & _ERR_CAPACITY:
+        raise _GatherOutTooSmall(f"gather_rows: out= does not fit this selection "
+                                 f"({capacity} entries for {nnz})", nnz)
+    res = {"offset": bufs["offset"][:n_sel + 1], "index": bufs["index"][:nnz],
+           "value": bufs["value"][:nnz] if value is not None else None}
+    if "field" in csr:
+        res["field"] = bufs["field"][:nnz] if field is not None else None
+    for k in cols:
+        res[k] = bufs[k][:n_sel]
+    res["_buffers"] = bufs
     return res
 
 

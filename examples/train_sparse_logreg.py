@@ -29,6 +29,10 @@ def main():
     ap.add_argument("--batch-rows", type=int, default=65536)
     ap.add_argument("--lr", type=float, default=0.5)
     ap.add_argument("--bucket-mb", type=float, default=64.0)
+    ap.add_argument("--shuffle-rows", action="store_true",
+                    help="a fresh row permutation of the resident CSR every epoch "
+                         "(data.RowBatches: device row gather) instead of file order")
+    ap.add_argument("--shuffle-seed", type=int, default=0)
     args = ap.parse_args()
 
     import torch
@@ -61,19 +65,33 @@ def main():
     opt = torch.optim.SGD(model.parameters(), lr=args.lr)
     n = csr.rows
     history = []
-    for epoch in range(args.epochs):
-        tot, cnt = 0.0, 0
+    shuffled = None
+    if args.shuffle_rows:
+        # every rank permutes its own rows; the seed differs per rank
+        shuffled = data.RowBatches({"offset": t["offset"], "index": t["index"], "value": t["value"],
+                                    "label": label}, args.batch_rows,
+                                   seed=args.shuffle_seed * world + rank)
+
+    def file_order():
         for b in range(0, n, args.batch_rows):
             e = min(n, b + args.batch_rows)
-            batch = {"offset": t["offset"][b:e + 1], "index": t["index"], "value": t["value"]}
+            yield {"offset": t["offset"][b:e + 1], "index": t["index"], "value": t["value"],
+                   "label": label[b:e]}
+
+    for epoch in range(args.epochs):
+        tot, cnt = 0.0, 0
+        if shuffled is not None:
+            shuffled.set_epoch(epoch)
+        for batch in (shuffled if shuffled is not None else file_order()):
             logits = model(batch)
-            loss = torch.nn.functional.binary_cross_entropy_with_logits(logits, label[b:e])
+            loss = torch.nn.functional.binary_cross_entropy_with_logits(logits, batch["label"])
             opt.zero_grad(set_to_none=False)
             loss.backward()
             reducer.synchronize()
             opt.step()
-            tot += float(loss.detach()) * (e - b)
-            cnt += e - b
+            rows_in = batch["label"].numel()
+            tot += float(loss.detach()) * rows_in
+            cnt += rows_in
         (loss_sum, rows_seen), _ = dist.global_stats([tot, cnt], 0)
         history.append(loss_sum / rows_seen)
     if rank == 0:

@@ -14,6 +14,8 @@
  *   K9 fp8 pack / hash   LaunchHashedDenseFP8     (feature_kernels.hip)
  *   K10 csr concat       LaunchCSRAppend          (feature_kernels.hip)
  *   K11 spmv / sdot      LaunchCSRSpMV, LaunchCSRSpMVT (feature_kernels.hip)
+ *   G1 row gather count  LaunchCSRGatherCount     (gather_kernels.hip)
+ *   G2 row gather fill   LaunchCSRGatherFill      (gather_kernels.hip)
  * All launchers are asynchronous on `stream` and never allocate or
  * synchronise (graph-capture safe, cdna_hip_programming.md Guideline 9).
  */
@@ -480,6 +482,52 @@ void LaunchCSRTranspose(const uint64_t* offset, size_t nrows, uint64_t base, uin
                         uint32_t* error, hipStream_t stream);
 size_t CSRTransposeScratchBytes(uint64_t nnz, uint64_t num_features);
 uint64_t CSRTransposeMaxFeatures();
+// ------------------- row gather (gather_kernels.hip) -------------------
+/*! \brief bits of the row gather's device error word */
+constexpr uint32_t kGatherErrRow = 1;       // a selected row id is >= nrows_src
+constexpr uint32_t kGatherErrCapacity = 2;  // the batch has more entries than out_capacity
+constexpr uint32_t kGatherErrSource = 4;    // a selected row's pointers do not fit the source arrays
+/*! \brief output entries one wave of LaunchCSRGatherFill owns */
+uint64_t CSRGatherRunEntries();
+/*! \brief u64 words of scan scratch for a selection of n_sel rows (ScanPartials + 2) */
+size_t CSRGatherScratchWords(size_t n_sel);
+/*!
+ * \brief G1: out_offset[i] = length of source row rows[i] (i < n_sel) and the
+ *  per-row columns that are non-null (label / weight / qid -> out_*).  rows:
+ *  n_sel int32 (rows64: int64) row ids of a CSR of nrows_src rows whose row
+ *  pointer `offset` may be a slice of a larger one (offset[0] != 0); in any
+ *  order, duplicates allowed.  An id >= nrows_src (a negative one is huge)
+ *  counts 0 entries, reads nothing, writes zeros and sets kGatherErrRow in
+ *  *error (device word, zeroed by the caller); a row whose pointers descend
+ *  or end past src_entries (entries of index / value / field) counts 0 and
+ *  sets kGatherErrSource.  Then scan out_offset in place with LaunchScanU64
+ *  (scratch: CSRGatherScratchWords) and pass its total to G2.
+ */
+void LaunchCSRGatherCount(const uint64_t* offset, uint64_t nrows_src, uint64_t src_entries,
+                          const void* rows, bool rows64, size_t n_sel, const float* label,
+                          const float* weight, const uint64_t* qid, uint64_t* out_offset,
+                          float* out_label, float* out_weight, uint64_t* out_qid, uint32_t* error,
+                          hipStream_t stream);
+/*!
+ * \brief G2: the entries of every selected row to their place in the batch:
+ *  out_*[p] = *[offset[rows[i]] + p - out_offset[i]] for out_offset[i] <= p <
+ *  out_offset[i + 1] (index, and value / field when non-null: a missing
+ *  column stays missing).  out_offset: G1's lengths scanned (n_sel + 1 slots;
+ *  the closing one is written here from *total, the scan's device total).  A
+ *  wave owns CSRGatherRunEntries() consecutive output entries.  Positions at
+ *  or past out_capacity (entries of out_*) are not written and set
+ *  kGatherErrCapacity; the launch is sized by out_capacity, the total being
+ *  known on the device only.  A source position at or past src_entries (the
+ *  row pointer changed after G1 checked it) is not read and sets
+ *  kGatherErrSource.  No atomics on the outputs.
+ */
+template <typename IndexType>
+void LaunchCSRGatherFill(const uint64_t* offset, uint64_t nrows_src, uint64_t src_entries,
+                         const void* rows, bool rows64, size_t n_sel, uint64_t* out_offset,
+                         const uint64_t* total, const IndexType* index, const float* value,
+                         const IndexType* field,
+                         IndexType* out_index, float* out_value, IndexType* out_field,
+                         uint64_t out_capacity, uint32_t* error, hipStream_t stream);
 /*! \brief fill n floats with v */
 void LaunchFill(float* p, size_t n, float v, hipStream_t stream);
 /*!

@@ -967,6 +967,65 @@ PYBIND11_MODULE(_dmlc, m) {
         py::arg("num_features"));
   m.def("csr_transpose_max_features", &gpu::CSRTransposeMaxFeatures);
   m.def(
+      "csr_gather_count",
+      [stream_of](uintptr_t offset, uint64_t nrows_src, uint64_t src_entries, uintptr_t rows,
+                  bool rows64, size_t n_sel, uintptr_t label, uintptr_t weight, uintptr_t qid,
+                  uintptr_t out_offset, uintptr_t out_label, uintptr_t out_weight,
+                  uintptr_t out_qid, uintptr_t scratch, uintptr_t total, uintptr_t error,
+                  uintptr_t stream) {
+        // G1 and the scan of its lengths: out_offset[0 .. n_sel) becomes the
+        // batch's row pointer, *total its entry count
+        auto* oo = reinterpret_cast<uint64_t*>(out_offset);
+        gpu::LaunchCSRGatherCount(
+            reinterpret_cast<const uint64_t*>(offset), nrows_src, src_entries,
+            reinterpret_cast<const void*>(rows), rows64, n_sel,
+            reinterpret_cast<const float*>(label), reinterpret_cast<const float*>(weight),
+            reinterpret_cast<const uint64_t*>(qid), oo, reinterpret_cast<float*>(out_label),
+            reinterpret_cast<float*>(out_weight), reinterpret_cast<uint64_t*>(out_qid),
+            reinterpret_cast<uint32_t*>(error), stream_of(stream));
+        gpu::LaunchScanU64(oo, n_sel, reinterpret_cast<uint64_t*>(scratch),
+                           reinterpret_cast<uint64_t*>(total), stream_of(stream));
+      },
+      py::arg("offset"), py::arg("nrows_src"), py::arg("src_entries"), py::arg("rows"),
+      py::arg("rows64"), py::arg("n_sel"), py::arg("label"), py::arg("weight"), py::arg("qid"),
+      py::arg("out_offset"), py::arg("out_label"), py::arg("out_weight"), py::arg("out_qid"),
+      py::arg("scratch"), py::arg("total"), py::arg("error"), py::arg("stream"));
+  m.def(
+      "csr_gather_fill",
+      [stream_of](uintptr_t offset, uint64_t nrows_src, uint64_t src_entries, uintptr_t rows,
+                  bool rows64, size_t n_sel, uintptr_t out_offset, uintptr_t total,
+                  uintptr_t index, uintptr_t value, uintptr_t field, uintptr_t out_index,
+                  uintptr_t out_value, uintptr_t out_field,
+                  uint64_t out_capacity, uintptr_t error, uintptr_t stream, bool index64) {
+        auto* off = reinterpret_cast<const uint64_t*>(offset);
+        auto* rw = reinterpret_cast<const void*>(rows);
+        auto* oo = reinterpret_cast<uint64_t*>(out_offset);
+        auto* tot = reinterpret_cast<const uint64_t*>(total);
+        auto* val = reinterpret_cast<const float*>(value);
+        auto* oval = reinterpret_cast<float*>(out_value);
+        auto* err = reinterpret_cast<uint32_t*>(error);
+        if (index64) {
+          gpu::LaunchCSRGatherFill<uint64_t>(
+              off, nrows_src, src_entries, rw, rows64, n_sel, oo, tot,
+              reinterpret_cast<const uint64_t*>(index), val,
+              reinterpret_cast<const uint64_t*>(field), reinterpret_cast<uint64_t*>(out_index), oval,
+              reinterpret_cast<uint64_t*>(out_field), out_capacity, err, stream_of(stream));
+        } else {
+          gpu::LaunchCSRGatherFill<uint32_t>(
+              off, nrows_src, src_entries, rw, rows64, n_sel, oo, tot,
+              reinterpret_cast<const uint32_t*>(index), val,
+              reinterpret_cast<const uint32_t*>(field), reinterpret_cast<uint32_t*>(out_index), oval,
+              reinterpret_cast<uint32_t*>(out_field), out_capacity, err, stream_of(stream));
+        }
+      },
+      py::arg("offset"), py::arg("nrows_src"), py::arg("src_entries"), py::arg("rows"),
+      py::arg("rows64"), py::arg("n_sel"), py::arg("out_offset"), py::arg("total"), py::arg("index"),
+      py::arg("value"), py::arg("field"), py::arg("out_index"), py::arg("out_value"),
+      py::arg("out_field"), py::arg("out_capacity"), py::arg("error"), py::arg("stream"),
+      py::arg("index64") = false);
+  m.def("csr_gather_scratch_words", &gpu::CSRGatherScratchWords, py::arg("n_sel"));
+  m.def("csr_gather_run_entries", &gpu::CSRGatherRunEntries);
+  m.def(
       "hashed_dense",
       [stream_of](uintptr_t offset, uintptr_t index, uintptr_t value, uintptr_t field,
                   size_t nrows, int dim, float scale, uint32_t seed, uintptr_t out, bool fp8,
