@@ -2,7 +2,7 @@
 
 The reference (dmlc-core) ships no model; its consumers (XGBoost, linear
 learners in ps-lite/rabit) train on RowBlocks.  These demonstrators close the
-loop on MI355X: device CSR from the GPU parser -> HIP SpMV -> loss ->
+loop on MI355X: device CSR from the GPU parser -> HIP SpMV / SpMM -> loss ->
 gradient all-reduced over RCCL.
 """
 from __future__ import annotations
@@ -11,9 +11,9 @@ from typing import Optional
 
 import torch
 
-from ..ops import csr_spmv, hashed_dense
+from ..ops import csr_spmm, csr_spmv, hashed_dense
 
-__all__ = ["SparseLogReg", "HashedFM"]
+__all__ = ["SparseLogReg", "HashedFM", "SparseSoftmaxReg", "SparseFM"]
 
 
 class SparseLogReg(torch.nn.Module):
@@ -35,6 +35,124 @@ class SparseLogReg(torch.nn.Module):
         w = csr.get("weight")
         return torch.nn.functional.binary_cross_entropy_with_logits(
             logits, label, weight=w, reduction="mean")
+
+
+def _dense(csr, num_features: int) -> torch.Tensor:
+    """the batch as a dense [rows, num_features] matrix (host tensors: the
+    formula the HIP kernels compute, for unit tests without a GPU)"""
+    from ..data import to_sparse_csr
+    return to_sparse_csr(csr, num_features).to_dense()
+
+
+class SparseSoftmaxReg(torch.nn.Module):
+    """Multiclass (softmax) regression on raw sparse features: logits =
+    X W + b with ``weight`` [F, C] and ``bias`` [C], both zero at the start;
+    labels are the class ids 0 .. C-1 of a multiclass LibSVM file.  On the
+    device the product is :func:`~dmlc_core_amd.ops.csr_spmm` (C up to 256,
+    feature ids < F unchecked); on host tensors the same formula runs on the
+    densified batch."""
+
+    def __init__(self, num_features: int, num_classes: int, grad: str = "auto"):
+        super().__init__()
+        self.num_features, self.num_classes = int(num_features), int(num_classes)
+        self.grad = grad  # X^T G: "auto" / "transpose" (cached inverted index) / "atomic"
+        self.weight = torch.nn.Parameter(
+            torch.zeros(self.num_features, self.num_classes, dtype=torch.float32))
+        self.bias = torch.nn.Parameter(torch.zeros(self.num_classes, dtype=torch.float32))
+
+    def forward(self, csr) -> torch.Tensor:
+        if not csr["index"].is_cuda:
+            return _dense(csr, self.num_features) @ self.weight + self.bias
+        return csr_spmm(csr, self.weight, self.bias, grad=self.grad)
+
+    def check_labels(self, label: torch.Tensor) -> None:
+        """``ValueError`` unless every label is an integer in [0, C): one
+        read of (min, max, all-integer) from the device"""
+        if label.numel() == 0:
+            return
+        lab = label.double()
+        lo, hi, whole = torch.stack([lab.min(), lab.max(),
+                                     (lab == lab.round()).all().double()]).tolist()
+        if not whole or not (0 <= lo and hi < self.num_classes):  # a NaN fails `whole`
+            raise ValueError(f"labels must be integers in [0, {self.num_classes}); "
+                             f"got min {lo}, max {hi}" + ("" if whole else ", not all integers"))
+
+    def loss(self, csr, validate: bool = True) -> torch.Tensor:
+        """Mean cross entropy against ``csr["label"]``; with a ``weight``
+        tensor in the dict ``mean(weight * ce)`` (SparseLogReg's convention).
+        ``validate`` checks the labels before any loss kernel runs: a label
+        outside [0, C) or a fractional one raises ``ValueError`` instead of
+        reaching torch's cross entropy (a device-side assert)."""
+        label = csr["label"]
+        if validate:
+            self.check_labels(label)
+        ce = torch.nn.functional.cross_entropy(self.forward(csr), label.long(), reduction="none")
+        w = csr.get("weight")
+        return (ce * w).mean() if w is not None else ce.mean()
+
+
+def _squared_values(csr):
+    """the dict sharing ``offset`` / ``index`` with ``csr`` and holding
+    ``value ** 2``, made once per CSR dict and cached in it (it carries its own
+    cached transpose); binary rows (no ``value``) are their own square"""
+    value = csr.get("value")
+    if value is None:
+        return csr
+    key = (int(value.data_ptr()), value.numel(), value._version)
+    cached = csr.get("_squared")
+    if cached is None or cached[0] != key:
+        cached = (key, {"offset": csr["offset"], "index": csr["index"], "value": value * value})
+        csr["_squared"] = cached
+    return cached[1]
+
+
+class SparseFM(torch.nn.Module):
+    """Factorisation machine on raw feature ids (no hashing):
+    ``y = b + x.w + 1/2 sum_f ((x V)_f^2 - (x^2 V^2)_f)`` with ``w`` [F, 1] and
+    ``v`` [F, rank].  On the device ``x V`` is
+    :func:`~dmlc_core_amd.ops.csr_spmm`, ``x.w`` and ``x^2 . rowsum(V^2)`` are
+    :func:`~dmlc_core_amd.ops.csr_spmv` (the latter over the CSR with squared
+    values), and autograd does the rest; rank up to 256, feature ids < F
+    unchecked.  On host tensors the same formula runs on the densified batch.
+    A row's feature ids are taken to be distinct, as in a LibSVM file: the
+    square of a densified row is then the row's squared values."""
+
+    def __init__(self, num_features: int, rank: int = 16, seed: int = 0):
+        super().__init__()
+        self.num_features, self.rank, self.seed = int(num_features), int(rank), int(seed)
+        g = torch.Generator(device="cpu")
+        g.manual_seed(self.seed)
+        self.bias = torch.nn.Parameter(torch.zeros(1))
+        self.w = torch.nn.Parameter(torch.zeros(self.num_features, 1))
+        self.v = torch.nn.Parameter(torch.randn(self.num_features, self.rank, generator=g) * 0.01)
+
+    def forward(self, csr) -> torch.Tensor:
+        if not csr["index"].is_cuda:
+            return self.reference(_dense(csr, self.num_features), self.w, self.v, self.bias)
+        zero = torch.zeros(1, dtype=torch.float32, device=self.w.device)
+        xv = csr_spmm(csr, self.v)
+        linear = csr_spmv(csr, self.w.reshape(-1), self.bias)
+        x2q = csr_spmv(_squared_values(csr), (self.v * self.v).sum(1), zero)
+        return linear + 0.5 * ((xv * xv).sum(1) - x2q)
+
+    def loss(self, csr, loss: str = "logistic") -> torch.Tensor:
+        """Mean ``"logistic"`` (labels in [0, 1]) or ``"squared"`` loss against
+        ``csr["label"]``, row-weighted by ``csr["weight"]`` if present
+        (``mean(weight * loss)``), as :meth:`HashedFM.loss`."""
+        if loss not in _FM_LOSSES:
+            raise ValueError(f"loss must be one of {sorted(_FM_LOSSES)}, got {loss!r}")
+        y = self.forward(csr)
+        lab, weight = csr["label"].to(y.dtype), csr.get("weight")
+        if loss == "logistic":
+            return torch.nn.functional.binary_cross_entropy_with_logits(y, lab, weight=weight)
+        err = (y - lab) ** 2
+        return (err * weight).mean() if weight is not None else err.mean()
+
+    @staticmethod
+    def reference(x: torch.Tensor, w, v, bias) -> torch.Tensor:
+        """fp32 reference of the same model on a dense batch
+        (:meth:`HashedFM.reference`)."""
+        return HashedFM.reference(x, w, v, bias)
 
 
 class _HashedFMFunction(torch.autograd.Function):

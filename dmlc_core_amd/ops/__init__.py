@@ -1,7 +1,8 @@
 """HIP (gfx950) kernels exposed as PyTorch operations on device CSR data.
 
 Every op launches a hand-written CDNA4 kernel from ``libdmlc.so`` on the
-current torch stream (src/gpu/feature_kernels.hip).  There is no PyTorch
+current torch stream (src/gpu/feature_kernels.hip, spmm_kernels.hip,
+transpose_kernels.hip, gather_kernels.hip).  There is no PyTorch
 fallback: on a machine without the extension or a GPU these functions raise.
 
 CSR arguments are the dict returned by :func:`dmlc_core_amd.data.csr_to_torch`
@@ -17,7 +18,8 @@ import torch
 from .. import _dmlc
 
 __all__ = ["spmv", "spmv_t", "hashed_dense", "SpMVFunction", "csr_spmv", "transpose",
-           "gather_rows", "gather_buffers", "release_workspace"]
+           "gather_rows", "gather_buffers", "release_workspace",
+           "spmm", "spmm_t", "SpMMFunction", "csr_spmm"]
 
 # persistent transpose scratch per (device, stream), grow-only: a rebuild (a
 # further shard, a refreshed batch) allocates no multi-GB scratch again
@@ -117,6 +119,81 @@ def spmv_t(csr: Dict, d: torch.Tensor, num_features: int) -> torch.Tensor:
     g = torch.zeros(num_features, dtype=torch.float32, device=d.device)
     nrows = csr["offset"].numel() - 1
     _dmlc.spmv_t(_ptr(csr["offset"]), _ptr(csr["index"]), _ptr(csr.get("value")), nrows, _ptr(d),
+                 _ptr(g), _stream(), _index64(csr))
+    return g
+
+
+def _check_dense(name: str, m, bias=None) -> int:
+    """the dense operand of :func:`spmm` / :func:`spmm_t` (and ``bias``), before
+    anything is launched; returns its column count k"""
+    if not isinstance(m, torch.Tensor) or m.dim() != 2:
+        raise ValueError(f"{name} must be a 2-D tensor [rows, k]")
+    if m.dtype != torch.float32:
+        raise ValueError(f"{name} must be float32, got {m.dtype}")
+    k, kmax = int(m.shape[1]), int(_dmlc.spmm_max_cols())
+    if not 1 <= k <= kmax:
+        raise ValueError(f"{name} must have 1 .. {kmax} columns, got {k}")
+    if not m.is_contiguous():
+        raise ValueError(f"{name} must be contiguous (row-major)")
+    if bias is not None:
+        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 \
+                or tuple(bias.shape) != (k,) or not bias.is_contiguous():
+            raise ValueError(f"bias must be a contiguous float32 tensor of shape [{k}]")
+    return k
+
+
+def _check_device(name: str, t, csr: Dict) -> None:
+    if t is not None and t.device != csr["index"].device:
+        raise ValueError(f"{name} must be on the CSR's device ({csr['index'].device}), "
+                         f"is on {t.device}")
+
+
+def spmm(csr: Dict, w: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Y[r, :] = sum_j value[j] * w[index[j], :] (+ bias)  (M1 / M1p,
+    src/gpu/spmm_kernels.hip): the CSR times a dense ``[F, k]`` matrix, as
+    float32 ``[rows, k]``.
+
+    ``w``: a contiguous float32 device tensor ``[F, k]`` with k from 1 to
+    ``_dmlc.spmm_max_cols()`` (256); ``bias``: None or a contiguous float32
+    device tensor ``[k]``; anything else raises ``ValueError`` before a
+    launch.  k a multiple of 4 reads ``w`` rows through 16-byte loads, other
+    widths through 4-byte loads.  Takes the CSR shapes of :func:`spmv`
+    (32- / 64-bit indices, ``value`` optional, ``offset`` a slice of a larger
+    row pointer, empty rows, no rows) and a transpose's interleaved pair
+    views.  Every feature id must be ``< w.shape[0]``: this precondition is
+    not checked on the device.  No atomics and a summation order fixed by k:
+    the same inputs give the same bytes."""
+    k = _check_dense("w", w, bias)
+    _check(csr, pairs=True)
+    _check_device("w", w, csr)
+    _check_device("bias", bias, csr)
+    nrows = csr["offset"].numel() - 1
+    y = torch.empty((nrows, k), dtype=torch.float32, device=w.device)
+    if _paired(csr):
+        _dmlc.spmm_pairs(_ptr(csr["offset"]), _ptr(csr["index"]), nrows, _ptr(w), _ptr(bias), k,
+                         _ptr(y), _stream())
+    else:
+        _dmlc.spmm(_ptr(csr["offset"]), _ptr(csr["index"]), _ptr(csr.get("value")), nrows, _ptr(w),
+                   _ptr(bias), k, _ptr(y), _stream(), _index64(csr))
+    return y
+
+
+def spmm_t(csr: Dict, d: torch.Tensor, num_features: int) -> torch.Tensor:
+    """G[index[j], :] += value[j] * d[row(j), :]  (M2, no-return f32 atomics
+    into a zeroed ``[num_features, k]`` result): X^T D without a transpose.
+    ``d``: a contiguous float32 device tensor ``[rows, k]``, validated as
+    :func:`spmm`'s ``w``.  A transpose's pair views are unpaired first.  Every
+    feature id must be ``< num_features`` (not checked on the device).  The
+    sums are in no fixed order."""
+    k = _check_dense("d", d)
+    csr = _unpair(csr)
+    _check(csr)
+    _check_device("d", d, csr)
+    nrows = csr["offset"].numel() - 1
+    if d.shape[0] != nrows:
+        raise ValueError(f"d has {d.shape[0]} rows, the CSR {nrows}")
+    g = torch.zeros((int(num_features), k), dtype=torch.float32, device=d.device)
+    _dmlc.spmm_t(_ptr(csr["offset"]), _ptr(csr["index"]), _ptr(csr.get("value")), nrows, _ptr(d), k,
                  _ptr(g), _stream(), _index64(csr))
     return g
 
@@ -412,6 +489,36 @@ def _whole(csr: Dict) -> bool:
         off.numel() * off.element_size() == off.untyped_storage().nbytes()
 
 
+def _cached_transpose(holder: Dict, csr: Dict, num_features: int, grad: str) -> Optional[Dict]:
+    """The transpose a backward of ``csr`` (the tensors of the dict ``holder``)
+    gathers over, or None for the atomic form.  Kept in ``holder['transpose']``
+    with the identity of its source (``_transpose_key``), so :func:`csr_spmv`
+    and :func:`csr_spmm` reuse each other's.  ``grad``: "atomic" never uses
+    one; "transpose" builds it on the first call; "auto" builds it on the first
+    call for a whole CSR and on the second through the same dict otherwise."""
+    if grad == "atomic":
+        return None
+    key = _source_key(csr, num_features)
+    t = holder.get("transpose")
+    if t is not None and holder.get("_transpose_key") != key:
+        t = None  # the dict now holds other tensors (or they were written in place)
+    if t is None:
+        uses = holder.get("_backward_calls", 0) + 1
+        if holder.get("_calls_key") != key:
+            uses = 1
+        holder["_backward_calls"] = uses
+        holder["_calls_key"] = key
+        # auto: only feature spaces the counting-sort transpose takes
+        # (<= 2^28 columns); wider models keep the atomic scatter, which
+        # has no column limit.  "transpose" asked for it: transpose() raises
+        fits = num_features <= _dmlc.csr_transpose_max_features()
+        if grad == "transpose" or (fits and (uses >= 2 or _whole(csr))):
+            t = transpose(csr, num_features)
+            holder["transpose"] = t
+            holder["_transpose_key"] = key
+    return t
+
+
 class SpMVFunction(torch.autograd.Function):
     """Autograd wrapper: forward = spmv, backward d/dw = X^T g -- a gather
     SpMV over the transpose cached in ``csr['transpose']``, or the f32-atomic
@@ -432,29 +539,41 @@ class SpMVFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         grad_out = grad_out.contiguous().float()
-        key = _source_key(ctx.csr, ctx.num_features)
-        t = ctx.holder.get("transpose")
-        if t is not None and ctx.holder.get("_transpose_key") != key:
-            t = None  # the dict now holds other tensors (or they were written in place)
-        if t is None and ctx.grad != "atomic":
-            uses = ctx.holder.get("_backward_calls", 0) + 1
-            if ctx.holder.get("_calls_key") != key:
-                uses = 1
-            ctx.holder["_backward_calls"] = uses
-            ctx.holder["_calls_key"] = key
-            # auto: only feature spaces the counting-sort transpose takes
-            # (<= 2^28 columns); wider models keep the atomic scatter, which
-            # has no column limit.  "transpose" asked for it: transpose() raises
-            fits = ctx.num_features <= _dmlc.csr_transpose_max_features()
-            if ctx.grad == "transpose" or (fits and (uses >= 2 or _whole(ctx.csr))):
-                t = transpose(ctx.csr, ctx.num_features)
-                ctx.holder["transpose"] = t
-                ctx.holder["_transpose_key"] = key
-        if t is not None and ctx.grad != "atomic":
+        t = _cached_transpose(ctx.holder, ctx.csr, ctx.num_features, ctx.grad)
+        if t is not None:
             gw = spmv(t, grad_out, 0.0)
         else:
             gw = spmv_t(ctx.csr, grad_out, ctx.num_features)
         gb = grad_out.sum().reshape(1)
+        return gw, gb, None, None, None
+
+
+class SpMMFunction(torch.autograd.Function):
+    """Autograd wrapper: forward = spmm(csr, w, bias), backward d/dw = X^T G --
+    the gather SpMM over the transpose cached in ``csr['transpose']`` (M1p),
+    or the f32-atomic spmm_t (M2) -- and d/dbias = column sums of G.  ``grad``
+    as for :class:`SpMVFunction`; both share one cache (:func:`_cached_transpose`)."""
+
+    @staticmethod
+    def forward(ctx, w, bias, csr_tuple, holder, grad):
+        offset, index, value = csr_tuple
+        ctx.csr = {"offset": offset, "index": index, "value": value}
+        ctx.holder, ctx.grad = holder, grad
+        ctx.num_features = w.shape[0]
+        return spmm(ctx.csr, w.detach(), None if bias is None else bias.detach())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        grad_out = grad_out.contiguous().float()
+        gw = gb = None
+        if ctx.needs_input_grad[0]:
+            t = _cached_transpose(ctx.holder, ctx.csr, ctx.num_features, ctx.grad)
+            if t is not None:
+                gw = spmm(t, grad_out)
+            else:
+                gw = spmm_t(ctx.csr, grad_out, ctx.num_features)
+        if ctx.needs_input_grad[1]:
+            gb = grad_out.sum(0)
         return gw, gb, None, None, None
 
 
@@ -471,3 +590,16 @@ def csr_spmv(csr: Dict, w: torch.Tensor, bias: torch.Tensor, grad: str = "auto")
     if grad not in ("auto", "transpose", "atomic"):
         raise ValueError(f"grad must be 'auto', 'transpose' or 'atomic', got {grad!r}")
     return SpMVFunction.apply(w, bias, (csr["offset"], csr["index"], csr.get("value")), csr, grad)
+
+
+def csr_spmm(csr: Dict, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
+             grad: str = "auto") -> torch.Tensor:
+    """Differentiable Y = X W + b for a device CSR batch and a dense ``[F, k]``
+    ``w`` (:func:`spmm`'s arguments and checks), differentiable in ``w`` and
+    ``bias``.  X^T G runs as the gather SpMM over the transpose cached in
+    ``csr['transpose']`` -- the one :func:`csr_spmv` uses, whichever of the two
+    built it -- or as the atomic :func:`spmm_t`; ``grad`` as for
+    :func:`csr_spmv`.  The "auto" policy is the one measured at k = 1."""
+    if grad not in ("auto", "transpose", "atomic"):
+        raise ValueError(f"grad must be 'auto', 'transpose' or 'atomic', got {grad!r}")
+    return SpMMFunction.apply(w, bias, (csr["offset"], csr["index"], csr.get("value")), csr, grad)

@@ -14,6 +14,9 @@
  *   K9 fp8 pack / hash   LaunchHashedDenseFP8     (feature_kernels.hip)
  *   K10 csr concat       LaunchCSRAppend          (feature_kernels.hip)
  *   K11 spmv / sdot      LaunchCSRSpMV, LaunchCSRSpMVT (feature_kernels.hip)
+ *   M1 spmm              LaunchCSRSpMM            (spmm_kernels.hip)
+ *   M1p spmm over pairs  LaunchCSRSpMMPairs       (spmm_kernels.hip)
+ *   M2 spmm transposed   LaunchCSRSpMMT           (spmm_kernels.hip)
  *   G1 row gather count  LaunchCSRGatherCount     (gather_kernels.hip)
  *   G2 row gather fill   LaunchCSRGatherFill      (gather_kernels.hip)
  * All launchers are asynchronous on `stream` and never allocate or
@@ -402,6 +405,34 @@ void LaunchCSRSpMV(const uint64_t* offset, const IndexType* index, const float* 
 template <typename IndexType>
 void LaunchCSRSpMVT(const uint64_t* offset, const IndexType* index, const float* value,
                     size_t nrows, const float* d, float* g, hipStream_t stream);
+// ------------------------- SpMM (spmm_kernels.hip) -------------------------
+/*! \brief widest dense operand (columns) of M1 / M1p / M2 */
+constexpr int kSpMMMaxCols = 256;
+/*!
+ * \brief M1: y[r, :] = sum_j value[j] * w[index[j], :] (+ bias[:]) for row-major
+ *  contiguous f32 w [features x k], y [nrows x k], bias [k] or nullptr; k in
+ *  1 .. kSpMMMaxCols.  The CSR shapes of K11: value may be nullptr (1.0 per
+ *  entry, a compile-time variant), offset may be a slice of a larger row
+ *  pointer, empty rows give bias or 0.  k % 4 == 0 with 16-byte aligned w, y
+ *  and bias takes 16-byte loads, anything else 4-byte loads.  No atomics and a
+ *  summation order fixed by k: the output bytes are a pure function of the
+ *  inputs.  Feature ids must be < features (not checked on the device).
+ */
+template <typename IndexType>
+void LaunchCSRSpMM(const uint64_t* offset, const IndexType* index, const float* value,
+                   size_t nrows, const float* w, const float* bias, int k, float* y,
+                   hipStream_t stream);
+/*! \brief M1p: M1 over the interleaved (u32 index, f32 value) pairs of a
+ *  transpose, one 8-byte load per entry; the same summation order as M1.  A
+ *  row of any length runs on one lane group of one wave. */
+void LaunchCSRSpMMPairs(const uint64_t* offset, const void* pairs, size_t nrows, const float* w,
+                        const float* bias, int k, float* y, hipStream_t stream);
+/*! \brief M2: g[index[j], :] += value[j] * d[r, :] with no-return f32 atomics
+ *  into a zeroed g [features x k]; the lanes of one entry cover one contiguous
+ *  4 * min(k, 64)-byte segment of a g row per wave-instruction */
+template <typename IndexType>
+void LaunchCSRSpMMT(const uint64_t* offset, const IndexType* index, const float* value,
+                    size_t nrows, const float* d, int k, float* g, hipStream_t stream);
 // ------------------------ HashedFM (fm_kernels.hip) ------------------------
 /*! \brief factor rank of the HIP HashedFM kernels and the [w | V] column count */
 constexpr int kFmRank = 16;

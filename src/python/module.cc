@@ -937,6 +937,58 @@ PYBIND11_MODULE(_dmlc, m) {
       py::arg("offset"), py::arg("index"), py::arg("value"), py::arg("nrows"), py::arg("d"),
       py::arg("g"), py::arg("stream"), py::arg("index64") = false);
   m.def(
+      "spmm",
+      [stream_of](uintptr_t offset, uintptr_t index, uintptr_t value, size_t nrows, uintptr_t w,
+                  uintptr_t bias, int k, uintptr_t y, uintptr_t stream, bool index64) {
+        auto* off = reinterpret_cast<const uint64_t*>(offset);
+        auto* val = reinterpret_cast<const float*>(value);
+        if (index64) {
+          gpu::LaunchCSRSpMM<uint64_t>(off, reinterpret_cast<const uint64_t*>(index), val, nrows,
+                                       reinterpret_cast<const float*>(w),
+                                       reinterpret_cast<const float*>(bias), k,
+                                       reinterpret_cast<float*>(y), stream_of(stream));
+        } else {
+          gpu::LaunchCSRSpMM<uint32_t>(off, reinterpret_cast<const uint32_t*>(index), val, nrows,
+                                       reinterpret_cast<const float*>(w),
+                                       reinterpret_cast<const float*>(bias), k,
+                                       reinterpret_cast<float*>(y), stream_of(stream));
+        }
+      },
+      py::arg("offset"), py::arg("index"), py::arg("value"), py::arg("nrows"), py::arg("w"),
+      py::arg("bias"), py::arg("k"), py::arg("y"), py::arg("stream"), py::arg("index64") = false);
+  m.def(
+      "spmm_pairs",
+      [stream_of](uintptr_t offset, uintptr_t pairs, size_t nrows, uintptr_t w, uintptr_t bias,
+                  int k, uintptr_t y, uintptr_t stream) {
+        gpu::LaunchCSRSpMMPairs(reinterpret_cast<const uint64_t*>(offset),
+                                reinterpret_cast<const void*>(pairs), nrows,
+                                reinterpret_cast<const float*>(w),
+                                reinterpret_cast<const float*>(bias), k,
+                                reinterpret_cast<float*>(y), stream_of(stream));
+      },
+      py::arg("offset"), py::arg("pairs"), py::arg("nrows"), py::arg("w"), py::arg("bias"),
+      py::arg("k"), py::arg("y"), py::arg("stream"));
+  m.def(
+      "spmm_t",
+      [stream_of](uintptr_t offset, uintptr_t index, uintptr_t value, size_t nrows, uintptr_t d,
+                  int k, uintptr_t g, uintptr_t stream, bool index64) {
+        auto* off = reinterpret_cast<const uint64_t*>(offset);
+        auto* val = reinterpret_cast<const float*>(value);
+        if (index64) {
+          gpu::LaunchCSRSpMMT<uint64_t>(off, reinterpret_cast<const uint64_t*>(index), val, nrows,
+                                        reinterpret_cast<const float*>(d), k,
+                                        reinterpret_cast<float*>(g), stream_of(stream));
+        } else {
+          gpu::LaunchCSRSpMMT<uint32_t>(off, reinterpret_cast<const uint32_t*>(index), val, nrows,
+                                        reinterpret_cast<const float*>(d), k,
+                                        reinterpret_cast<float*>(g), stream_of(stream));
+        }
+      },
+      py::arg("offset"), py::arg("index"), py::arg("value"), py::arg("nrows"), py::arg("d"),
+      py::arg("k"), py::arg("g"), py::arg("stream"), py::arg("index64") = false);
+  m.def("spmm_max_cols", []() { return gpu::kSpMMMaxCols; },
+        "widest dense operand (columns) ops.spmm / ops.spmm_t take");
+  m.def(
       "csr_transpose",
       [stream_of](uintptr_t offset, size_t nrows, uint64_t base, uint64_t nnz, uintptr_t index,
                   uintptr_t value, uint64_t num_features, uintptr_t col_ptr, uintptr_t row_out,
