@@ -7,6 +7,9 @@
 #   nostore   DMLC_CSV_EXP=2: decoded, no CSR stores
 #   neither   DMLC_CSV_EXP=3
 #   norounds  DMLC_CSV_EXP=4: masks, scans and listing only
+# The DMLC_CSV_EXP experiments exist only in a pricing build of the kernels
+# (production kernels hold no experiment branches and ignore the variable):
+#   make clean && make HIPFLAGS_EXTRA=-DDMLC_PRICING all
 # usage (through gpurun): bash scripts/csv_pricing.sh OUTDIR
 set -o pipefail
 root="${GRAFT_REPO_ROOT:-$(pwd)}"

@@ -2,6 +2,9 @@
 # Price the HBM-resident RecordIO decode: bench.py --mode hbm --format recordio
 # under kernel traces -- counted path (default), one pass, and one-pass
 # ablations (DMLC_REC_EXP: 1 no look-back wait, 2 no payload copies).
+# The DMLC_REC_EXP experiments exist only in a pricing build of the kernels
+# (production kernels hold no experiment branches and ignore the variable):
+#   make clean && make HIPFLAGS_EXTRA=-DDMLC_PRICING all
 # usage (through gpurun): bash scripts/rec_pricing.sh OUTDIR
 set -o pipefail
 root="${GRAFT_REPO_ROOT:-$(pwd)}"

@@ -446,9 +446,9 @@ __device__ __noinline__ GenericField generic_field(const char* q, const char* en
 
 // 6 waves per SIMD (the LDS allows 6 workgroups per CU): <= 84 VGPRs.
 // kCol0: the common configuration compiled on its own -- positional counts
-// (label column 0 or none), no weight column, no pricing experiments: the
-// round loop loses the weight / short-row / experiment branches and the
-// scalar registers they held (the general kernel sits at the SGPR limit)
+// (label column 0 or none), no weight column: the round loop loses the
+// weight / short-row branches and the scalar registers they held (the
+// general kernel sits at the SGPR limit)
 template <typename IndexType, bool kCol0>
 __global__ __launch_bounds__(kThreads)
 __attribute__((amdgpu_waves_per_eu(6))) void k_csv_tile_fill(const uint8_t* __restrict__ text,
@@ -458,7 +458,7 @@ __attribute__((amdgpu_waves_per_eu(6))) void k_csv_tile_fill(const uint8_t* __re
                                                             FillTarget<IndexType> out,
                                                             MetaPartial* __restrict__ partials,
                                                             uint32_t exp_arg) {
-  const uint32_t exp = kCol0 ? 0u : exp_arg;
+  const uint32_t exp = dev::pricing_exp(exp_arg);  // 0 outside a DMLC_PRICING build
   __shared__ uint4 s_ring[kWaves][kRingVecs];
   __shared__ uint2 s_list[kWaves][kListCap];
   const int lane = lane_id();
@@ -579,7 +579,7 @@ __attribute__((amdgpu_waves_per_eu(6))) void k_csv_tile_fill(const uint8_t* __re
     w.excl += f21(sl.total, 2);
     irregular |= nf > kListCap;
     wave_sync();
-    // pricing experiments (DMLC_CSV_EXP, 0 in production): 4 skips the rounds
+    // pricing experiments (DMLC_CSV_EXP in a DMLC_PRICING build): 4 skips the rounds
     const uint32_t nlist = (exp & 4u) ? 0u : (nf < kListCap ? nf : kListCap);
     for (uint32_t r0 = 0; r0 < nlist; r0 += kWave) {
       const uint32_t k = r0 + lane;
@@ -694,12 +694,7 @@ CsvCfg MakeCfg(int label_column, int weight_column, char delimiter) {
   c.zero_excl = (c.label_col == 0 ? 1 : 0) + (c.weight_col == 0 ? 1 : 0);
   c.delim = static_cast<uint8_t>(delimiter);
   // positional counts whenever no column numbers are needed
-  // (DMLC_CSV_POSCOUNT=0: the owning-tile count S1 for every chunk)
-  static const bool pos_ok = [] {
-    const char* v = std::getenv("DMLC_CSV_POSCOUNT");
-    return v == nullptr || std::atoi(v) != 0;
-  }();
-  c.pos = pos_ok && c.label_col <= 0 && c.weight_col <= 0 ? 1 : 0;
+  c.pos = c.label_col <= 0 && c.weight_col <= 0 ? 1 : 0;
   return c;
 }
 
@@ -730,16 +725,13 @@ void LaunchCsvTileFill(const char* text, size_t nbytes, int label_column, int we
                        hipStream_t stream) {
   const size_t ntiles = TileCount(nbytes);
   if (ntiles == 0) return;
-  static const uint32_t exp = [] {
-    const char* v = std::getenv("DMLC_CSV_EXP");
-    return v != nullptr ? static_cast<uint32_t>(std::atoi(v)) : 0u;
-  }();
+  static const uint32_t exp = dev::pricing_env("DMLC_CSV_EXP");
   const CsvCfg cfg = MakeCfg(label_column, weight_column, delimiter);
   const dim3 grid((ntiles + kWaves - 1) / kWaves);
   const uint8_t* t = reinterpret_cast<const uint8_t*>(text);
-  if (cfg.pos && !cfg.has_weight && exp == 0) {
+  if (cfg.pos && !cfg.has_weight) {
     hipLaunchKernelGGL((k_csv_tile_fill<IndexType, true>), grid, dim3(kThreads), 0, stream, t, nbytes,
-                       ntiles, cfg, tile_prefix, tile_masks, out, partials, 0u);
+                       ntiles, cfg, tile_prefix, tile_masks, out, partials, exp);
   } else {
     hipLaunchKernelGGL((k_csv_tile_fill<IndexType, false>), grid, dim3(kThreads), 0, stream, t,
                        nbytes, ntiles, cfg, tile_prefix, tile_masks, out, partials, exp);

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdlib>
 #include <type_traits>
 
 namespace dmlc {
@@ -19,6 +20,34 @@ namespace gpu {
 namespace dev {
 
 constexpr int kWave = 64;
+
+/*!
+ * \brief Pricing experiments (scripts/fill_pricing.sh, csv_pricing.sh,
+ *  rec_pricing.sh: a kernel with one of its stages skipped, to price that
+ *  stage; its outputs are wrong) exist only in a
+ *  build with -DDMLC_PRICING.  The host half reads an experiment variable
+ *  (DMLC_FILL_EXP, DMLC_CSV_EXP, DMLC_REC_EXP) and the device half passes the
+ *  value on; in every other build both are the constant 0, so a production
+ *  kernel compiles without its experiment branches, holds no experiment flag
+ *  in a register, and no environment variable changes what it computes.
+ */
+inline uint32_t pricing_env(const char* name) {
+#ifdef DMLC_PRICING
+  const char* v = std::getenv(name);
+  return v != nullptr ? static_cast<uint32_t>(std::atoi(v)) : 0u;
+#else
+  (void)name;
+  return 0u;
+#endif
+}
+__device__ __forceinline__ uint32_t pricing_exp(uint32_t exp) {
+#ifdef DMLC_PRICING
+  return exp;
+#else
+  (void)exp;
+  return 0u;
+#endif
+}
 
 __device__ __forceinline__ int lane_id() { return __lane_id(); }
 
@@ -194,35 +223,50 @@ __device__ __forceinline__ T wave_or(T v) {
 }
 
 /*!
+ * \brief reduce (max, max, or) over a workgroup of kBlock threads: on return
+ *  thread 0 holds the block's result in *mi, *mf, *fl (the other threads hold
+ *  partial folds).  Every thread of the block must call it; contains a
+ *  __syncthreads.
+ */
+template <int kBlock>
+__device__ __forceinline__ void block_fold_meta(unsigned long long* mi, unsigned long long* mf,
+                                                unsigned* fl) {
+  constexpr int kWaves = kBlock / kWave;
+  __shared__ unsigned long long s_mi[kWaves], s_mf[kWaves];
+  __shared__ unsigned s_fl[kWaves];
+  *mi = wave_max(*mi);
+  *mf = wave_max(*mf);
+  *fl = wave_or(*fl);
+  const int wid = threadIdx.x / kWave;
+  if (lane_id() == 0) {
+    s_mi[wid] = *mi;
+    s_mf[wid] = *mf;
+    s_fl[wid] = *fl;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < kWaves; ++w) {
+      *mi = s_mi[w] > *mi ? s_mi[w] : *mi;
+      *mf = s_mf[w] > *mf ? s_mf[w] : *mf;
+      *fl |= s_fl[w];
+    }
+  }
+}
+
+/*!
  * \brief reduce (max, max, or) over a 256-thread workgroup and store the
  *  result in slot blockIdx.x — every thread of the block must call it.
  */
 template <typename Partial>
 __device__ __forceinline__ void block_store_partial(unsigned long long mi, unsigned long long mf,
                                                     unsigned fl, Partial* partials) {
-  __shared__ unsigned long long s_mi[4], s_mf[4];
-  __shared__ unsigned s_fl[4];
-  mi = wave_max(mi);
-  mf = wave_max(mf);
-  fl = wave_or(fl);
-  const int wid = threadIdx.x / kWave;
-  if (lane_id() == 0) {
-    s_mi[wid] = mi;
-    s_mf[wid] = mf;
-    s_fl[wid] = fl;
-  }
-  __syncthreads();
+  block_fold_meta<256>(&mi, &mf, &fl);
   if (threadIdx.x == 0) {
     Partial p;
-    p.max_index = s_mi[0];
-    p.max_field = s_mf[0];
-    p.flags = s_fl[0];
+    p.max_index = mi;
+    p.max_field = mf;
+    p.flags = fl;
     p.pad = 0;
-    for (int w = 1; w < static_cast<int>(blockDim.x) / kWave; ++w) {
-      p.max_index = s_mi[w] > p.max_index ? s_mi[w] : p.max_index;
-      p.max_field = s_mf[w] > p.max_field ? s_mf[w] : p.max_field;
-      p.flags |= s_fl[w];
-    }
     partials[blockIdx.x] = p;
   }
 }

@@ -272,7 +272,7 @@ struct RecPass {
   ChunkMeta* meta;             // records / bytes of the chunk (the last tile writes them)
   uint64_t rec_cap, byte_cap;  // offset / data capacity: records / bytes past them are not
                                // written and set kFlagOverflow (grow, run again)
-  uint32_t exp;                // pricing experiments (DMLC_REC_EXP; 0 in production): 1 no
+  uint32_t exp;                // pricing experiments (DMLC_REC_EXP in a DMLC_PRICING build): 1 no
                                // look-back wait (wrong positions), 2 no payload copies
 };
 
@@ -334,7 +334,7 @@ __global__ __launch_bounds__(kThreads) void k_rec_tile_fill(const uint32_t* __re
     if (tile == 0 && lane == 0 && n != 0 && !(t.q[0].x == kMagic && n > 1 && cflag_of(t.q[0].y) <= 1))
       err |= kRecErrBadPart;  // a chunk starts at a record head
     c = wave_sum_2x32(c);
-    if (op.exp & 1u) {
+    if (pricing_exp(op.exp) & 1u) {
       pre = static_cast<uint64_t>(tile) * c;  // pricing: positions without the look-back
     } else {
       pre = lookback_pairs<32>(op.status, tile, c, lane);
@@ -438,7 +438,7 @@ __global__ __launch_bounds__(kThreads) void k_rec_tile_fill(const uint32_t* __re
   // a block's 16 source bytes are five payload words funnel-shifted into
   // place, read from the LDS-staged tile (or from memory past the tile).
   const int hl = lane & 31;
-  for (uint32_t e0 = 0; e0 < ((op.exp & 2u) ? 0u : nbig); e0 += 2) {
+  for (uint32_t e0 = 0; e0 < ((pricing_exp(op.exp) & 2u) ? 0u : nbig); e0 += 2) {
     const uint32_t e = e0 + static_cast<uint32_t>(lane >> 5);
     if (e < nbig) {
       const BigPart bp = big[e];
@@ -544,8 +544,10 @@ void LaunchRecordIOTileCountChain(const uint32_t* words, size_t nwords, uint64_t
   if (tiles == 0) return;
   // large pieces (counted beside a fill): up to 16 tiles per lane, so the
   // latency-bound chain waves hold few CU slots; small ones: a lane per tile
-  // (DMLC_REC_CHAIN_TILES forces a tiles-per-lane value: the tests' small
-  // chunks exercise the multi-tile walk with it)
+  // DMLC_REC_CHAIN_TILES forces a tiles-per-lane value.  It stays a run-time
+  // variable in every build: tests/test_gpu_recordio.py reaches the
+  // multi-tile chain walk at test sizes with it, and every value gives the
+  // same outputs (it only changes how the walk is split over lanes)
   static const size_t forced = [] {
     const char* v = std::getenv("DMLC_REC_CHAIN_TILES");
     return v != nullptr ? static_cast<size_t>(std::atoi(v)) : size_t(0);
@@ -567,10 +569,7 @@ size_t LaunchRecordIOTileFill(const uint32_t* words, size_t nwords, const uint64
   const size_t tiles = RecordIOTiles(nwords);
   if (tiles == 0) return 0;
   const size_t groups = (tiles + kWaves - 1) / kWaves;
-  static const uint32_t exp = [] {
-    const char* v = std::getenv("DMLC_REC_EXP");
-    return v != nullptr ? static_cast<uint32_t>(std::atoi(v)) : 0u;
-  }();
+  static const uint32_t exp = pricing_env("DMLC_REC_EXP");
   RecPass op{nullptr, nullptr, 0ull, nullptr, ~0ull, ~0ull, exp};
   if (caps != nullptr) {
     op.meta = caps->meta;

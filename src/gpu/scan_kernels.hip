@@ -112,28 +112,12 @@ __global__ __launch_bounds__(kThreads) void k_reduce_partials(const MetaPartial*
     mf = q.max_field > mf ? q.max_field : mf;
     fl |= q.flags;
   }
-  __shared__ unsigned long long s_mi[4], s_mf[4];
-  __shared__ unsigned s_fl[4];
-  mi = dev::wave_max(mi);
-  mf = dev::wave_max(mf);
-  fl = dev::wave_or(fl);
-  const int wid = threadIdx.x / dev::kWave;
-  if (dev::lane_id() == 0) {
-    s_mi[wid] = mi;
-    s_mf[wid] = mf;
-    s_fl[wid] = fl;
-  }
-  __syncthreads();
+  dev::block_fold_meta<kThreads>(&mi, &mf, &fl);
   if (threadIdx.x == 0) {
-    for (int w = 1; w < 4; ++w) {
-      s_mi[0] = s_mi[w] > s_mi[0] ? s_mi[w] : s_mi[0];
-      s_mf[0] = s_mf[w] > s_mf[0] ? s_mf[w] : s_mf[0];
-      s_fl[0] |= s_fl[w];
-    }
     // single writer, stream ordered: merge into what earlier kernels stored
-    meta->max_index = s_mi[0] > meta->max_index ? s_mi[0] : meta->max_index;
-    meta->max_field = s_mf[0] > meta->max_field ? s_mf[0] : meta->max_field;
-    meta->flags |= s_fl[0];
+    meta->max_index = mi > meta->max_index ? mi : meta->max_index;
+    meta->max_field = mf > meta->max_field ? mf : meta->max_field;
+    meta->flags |= fl;
   }
 }
 

@@ -907,22 +907,10 @@ struct FillPass {
   unsigned long long* ticket;   // workgroup ticket counter
   unsigned long long ticket0;   // its value at this launch
   ChunkMeta* meta;              // nlines / nrows / nnz of the chunk (the last tile writes them)
-  uint32_t exp;                 // pricing experiments (DMLC_FILL_EXP; 0 in production):
+  uint32_t exp;                 // pricing experiments (DMLC_FILL_EXP in a DMLC_PRICING build):
                                 // 1 no CSR stores, 2 no token decode (outputs are wrong)
   const uint32_t* masks;        // counted path: C1's start masks (TileMaskWords)
 };
-
-/*! \brief the pricing experiments of a DMLC_FILL_PRICING build (scripts/
- *  fill_pricing.sh); a constant 0 otherwise, so production kernels hold no
- *  experiment flags in scalar registers (the fill is at the SGPR limit) */
-__device__ __forceinline__ uint32_t fill_exp(const FillPass& op) {
-#ifdef DMLC_FILL_PRICING
-  return op.exp;
-#else
-  (void)op;
-  return 0u;
-#endif
-}
 
 // kLean: a target without qid / weight columns (the common case) compiled on
 // its own -- no qid pass, no weight stores, one flag for "weights seen": the
@@ -1205,7 +1193,7 @@ __global__ __launch_bounds__(kThreads, DMLC_FILL_WAVES) void k_tile_fill(
       } else {
         irregular |= active & !room_ok;
       }
-      if (fill_exp(op) & 1u) {
+      if (dev::pricing_exp(op.exp) & 1u) {
         // pricing: everything but the stores (the values stay live)
         sink ^= (active ? __float_as_uint(t.f0) ^ t.u0 ^ t.u1 : 0u) + static_cast<uint32_t>(i);
         return;
@@ -1276,7 +1264,7 @@ __global__ __launch_bounds__(kThreads, DMLC_FILL_WAVES) void k_tile_fill(
         ta.u0_hi = ta.u1_hi = tb.u0_hi = tb.u1_hi = 0;
         ta.u1 = tb.u1 = 0;
         bool oka, okb;
-        if (fill_exp(op) & 2u) {  // pricing: no decode
+        if (dev::pricing_exp(op.exp) & 2u) {  // pricing: no decode
           ta.u0 = ea;
           tb.u0 = eb;
           ta.f0 = ta.f1 = tb.f0 = tb.f1 = 1.0f;
@@ -1845,27 +1833,11 @@ __global__ __launch_bounds__(kFinishThreads) void k_tile_finish(
       fl |= q[u].flags;
     }
   }
-  __shared__ unsigned long long s_mi[kFinishThreads / 64], s_mf[kFinishThreads / 64];
-  __shared__ unsigned s_fl[kFinishThreads / 64];
-  mi = dev::wave_max(mi);
-  mf = dev::wave_max(mf);
-  fl = dev::wave_or(fl);
-  const int wid = threadIdx.x / dev::kWave;
-  if (dev::lane_id() == 0) {
-    s_mi[wid] = mi;
-    s_mf[wid] = mf;
-    s_fl[wid] = fl;
-  }
-  __syncthreads();
+  dev::block_fold_meta<kFinishThreads>(&mi, &mf, &fl);
   if (threadIdx.x == 0) {
-    for (int w = 1; w < kFinishThreads / 64; ++w) {
-      s_mi[0] = s_mi[w] > s_mi[0] ? s_mi[w] : s_mi[0];
-      s_mf[0] = s_mf[w] > s_mf[0] ? s_mf[w] : s_mf[0];
-      s_fl[0] |= s_fl[w];
-    }
-    meta->max_index = s_mi[0];
-    meta->max_field = s_mf[0];
-    meta->flags |= s_fl[0];
+    meta->max_index = mi;
+    meta->max_field = mf;
+    meta->flags |= fl;
     // (an overflowed one-pass fill's rows reach past the target: no row pointer)
     if (offset != nullptr && !(meta->flags & kFlagOverflow)) {
       offset[row_base + meta->nrows] = nnz_base + meta->nnz;
@@ -1886,31 +1858,12 @@ __global__ __launch_bounds__(kFinishThreads) void k_tile_finish_partial(
     mf = q.max_field > mf ? q.max_field : mf;
     fl |= q.flags;
   }
-  __shared__ unsigned long long s_mi[kFinishThreads / 64], s_mf[kFinishThreads / 64];
-  __shared__ unsigned s_fl[kFinishThreads / 64];
-  mi = dev::wave_max(mi);
-  mf = dev::wave_max(mf);
-  fl = dev::wave_or(fl);
-  const int wid = threadIdx.x / dev::kWave;
-  if (dev::lane_id() == 0) {
-    s_mi[wid] = mi;
-    s_mf[wid] = mf;
-    s_fl[wid] = fl;
-  }
-  __syncthreads();
+  dev::block_fold_meta<kFinishThreads>(&mi, &mf, &fl);
   if (threadIdx.x == 0) {
-    for (int w = 1; w < kFinishThreads / 64; ++w) {
-      mi = s_mi[w] > mi ? s_mi[w] : mi;
-      mf = s_mf[w] > mf ? s_mf[w] : mf;
-    }
-    mi = s_mi[0] > mi ? s_mi[0] : mi;
-    mf = s_mf[0] > mf ? s_mf[0] : mf;
-    unsigned f = 0;
-    for (int w = 0; w < kFinishThreads / 64; ++w) f |= s_fl[w];
     MetaPartial r;
     r.max_index = mi;
     r.max_field = mf;
-    r.flags = f;
+    r.flags = fl;
     r.pad = 0;
     out[blockIdx.x] = r;
   }
@@ -1999,10 +1952,7 @@ size_t LaunchTileFill(const char* text, size_t nbytes, TextFormat format,
   const size_t ntiles = TileCount(nbytes);
   const uint8_t* t = reinterpret_cast<const uint8_t*>(text);
   const size_t groups = (ntiles + kFillWaves - 1) / kFillWaves;
-  static const uint32_t exp = [] {
-    const char* v = std::getenv("DMLC_FILL_EXP");
-    return v != nullptr ? static_cast<uint32_t>(std::atoi(v)) : 0u;
-  }();
+  static const uint32_t exp = dev::pricing_env("DMLC_FILL_EXP");
   FillPass op{nullptr, nullptr, 0ull, meta, exp, tile_masks};
   CHECK(one_pass != nullptr || tile_masks != nullptr || ntiles == 0)
       << "LaunchTileFill: the counted path needs C1's tile_masks";

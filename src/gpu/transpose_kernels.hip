@@ -12,7 +12,7 @@
  *  bucket (kB = 10 .. 12, LowBits: the narrowest that keeps at most
  *  kMaxBuckets buckets, so feature ids < 2^22; wider feature spaces, up to
  *  2^28, take the three-level sort of RunSort3 below):
- *   T1 k_bucket_hist  one workgroup per block of BlockSubs() sub-tiles (in CSR
+ *   T1 k_bucket_hist  one workgroup per block of kBlockSubs sub-tiles (in CSR
  *      order): LDS histogram of buckets -> G[bucket][block].
  *   T2 exclusive scan of G (bucket-major): where each (bucket, block) run
  *      lands in the bucket-ordered intermediate arrays.
@@ -27,12 +27,14 @@
  *      400 M entries).  Writes the low key (u16) and the (row, value) pair
  *      (8 bytes; the row alone without values).  The next sub-tile's
  *      entries load while this one is sorted.
- *   T4a k_lowkey_hist  one workgroup per (bucket, segment) of the bucket: LDS
+ *   T4 the digit pass (k_digit_*: one stable counting-sort pass, shared with
+ *      L2 of the three-level sort) over the whole low key:
+ *   T4a k_digit_hist  one workgroup per (bucket, segment) of the bucket: LDS
  *      histogram of the L low keys -> H[bucket][segment][L].
- *   T4b k_lowkey_scan  one workgroup per bucket: column totals over segments,
+ *   T4b k_digit_scan  one workgroup per bucket: column totals over segments,
  *      exclusive scan over the bucket's columns -> col_ptr, and per-segment
  *      starting cursors (in place in H).
- *   T4c k_lowkey_scatter  one wave per (bucket, segment): cursors in LDS,
+ *   T4c k_digit_scatter  one wave per (bucket, segment): cursors in LDS,
  *      the segment's entries in order (8 groups of 64 loaded a batch ahead),
  *      ranks by ballots over the low-key bits -> row / value at their final
  *      CSC position.
@@ -42,8 +44,6 @@
 #include <dmlc/gpu/hip_utils.h>
 #include <dmlc/logging.h>
 #include <hip/hip_runtime.h>
-
-#include <cstdlib>
 
 #include "./device_common.h"
 #include "./kernels.h"
@@ -56,13 +56,14 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / dev::kWave;
 constexpr int kMinLowBits = 10;  // columns per bucket: 2^kB, kB = 10 .. 12 (LowBits)
 constexpr int kMaxLowBits = 12;
-constexpr int kDefaultLowBits = kMinLowBits;
 constexpr uint32_t kMaxBuckets = 1024;
 constexpr uint32_t kSubElems = 2048;        // T3 sub-tile, sorted in LDS (4 workgroups / CU)
-constexpr int kBlockSubs = 15;  // sub-tiles per T1 / T3 block (a workgroup), BlockSubs()
+// sub-tiles per T1 / T3 block (a workgroup): fewer blocks shrink G (buckets x
+// blocks, written by T1 column by column)
+constexpr int kBlockSubs = 15;
 constexpr uint32_t kChunk = kSubElems / kWaves;  // entries per wave per sub-tile
 constexpr int kPerLane = kChunk / dev::kWave;
-constexpr int kSegments = 16;              // T4 segments per bucket
+constexpr int kSegments = 16;  // segments per bucket of a digit pass (T4, L2)
 
 /*! \brief a feature id as a column below num_features (out-of-range ids are
  *  clamped for memory safety and reported through the error word by T1) */
@@ -346,46 +347,78 @@ __global__ __launch_bounds__(kThreads) void k_bucket_scatter(
   }
 }
 
-/*! \brief [begin, end) of segment s of bucket b (T4), from the bucket starts */
-__device__ __forceinline__ void segment(const uint64_t* __restrict__ bstart, uint32_t b, int s,
-                                        uint64_t* begin, uint64_t* end) {
+// ---------------------------------------------------------------------------
+// The digit pass: one stable counting-sort pass over every bucket, by the
+// digit (key >> kShift) & (2^kB - 1) of its entries, in kSeg segments per
+// bucket.  T4 is this pass at (u16 keys, shift 0, the kB low-key bits) into
+// the CSC and its column pointer; L2 of the three-level sort below is it at
+// (u32 keys, shift 8, S - 8 bits) into the super-bucket order.
+
+/*! \brief [begin, end) of segment s of kSeg segments of bucket b, from the bucket starts */
+template <int kSeg>
+__device__ __forceinline__ void seg_range(const uint64_t* __restrict__ bstart, uint32_t b, int s,
+                                          uint64_t* begin, uint64_t* end) {
   const uint64_t b0 = bstart[b], b1 = bstart[b + 1];
   const uint64_t n = b1 - b0;
-  *begin = b0 + n * static_cast<uint64_t>(s) / kSegments;
-  *end = b0 + n * static_cast<uint64_t>(s + 1) / kSegments;
+  *begin = b0 + n * static_cast<uint64_t>(s) / kSeg;
+  *end = b0 + n * static_cast<uint64_t>(s + 1) / kSeg;
 }
 
-template <int kB>
-__global__ __launch_bounds__(kThreads) void k_lowkey_hist(const uint16_t* __restrict__ t_key,
-                                                          const uint64_t* __restrict__ bstart,
-                                                          uint32_t* __restrict__ H) {
+/*! \brief the digit of a key.  Contract of a pass at shift 0: every key is
+ *  below 2^kB already (T3 writes T4's keys masked; nothing else writes them),
+ *  since the key itself indexes the LDS histogram and cursor tables.  It is
+ *  taken as it is: masked again, the compiler narrows every key right behind
+ *  its load, and the scatter then waits for the loads of a batch one by one
+ *  (17 more s_waitcnt in the kernel) instead of once per batch */
+template <int kShift, int kB>
+__device__ __forceinline__ uint32_t digit_of(uint32_t key) {
+  if constexpr (kShift == 0) {
+    return key;
+  } else {
+    return (key >> kShift) & ((1u << kB) - 1u);
+  }
+}
+
+/*! \brief digit histogram: one workgroup per (bucket, segment), an LDS
+ *  histogram of its entries' digits -> H[bucket][segment][2^kB] */
+template <typename KeyIn, int kShift, int kB, int kSeg>
+__global__ __launch_bounds__(kThreads) void k_digit_hist(const KeyIn* __restrict__ key,
+                                                         const uint64_t* __restrict__ bstart,
+                                                         uint32_t* __restrict__ H) {
+  static_assert(sizeof(KeyIn) == 2 || sizeof(KeyIn) == 4, "u16 or u32 keys");
   constexpr uint32_t kLow = 1u << kB;
+  constexpr uint64_t kVec = 16 / sizeof(KeyIn);  // keys per 16-byte load
   // counts need no order: the whole workgroup shares one histogram
   __shared__ uint32_t hist[kLow];
-  const uint32_t b = blockIdx.x / kSegments;
-  const int s = static_cast<int>(blockIdx.x % kSegments);
+  const uint32_t b = blockIdx.x / kSeg;
+  const int s = static_cast<int>(blockIdx.x % kSeg);
   for (uint32_t c = threadIdx.x; c < kLow; c += kThreads) hist[c] = 0;
   __syncthreads();
   uint64_t e0, e1;
-  segment(bstart, b, s, &e0, &e1);
-  // eight keys per 16-byte load over the aligned middle of the segment, the
-  // unaligned head and tail one key at a time
-  const uint64_t a0 = (e0 + 7) & ~7ull, a1 = e1 & ~7ull;
+  seg_range<kSeg>(bstart, b, s, &e0, &e1);
+  auto add = [&](uint32_t k) { atomicAdd(&hist[digit_of<kShift, kB>(k)], 1u); };
+  // eight u16 / four u32 keys per 16-byte load over the aligned middle of the
+  // segment, the unaligned head and tail one key at a time
+  const uint64_t a0 = (e0 + kVec - 1) & ~(kVec - 1), a1 = e1 & ~(kVec - 1);
   if (a0 >= a1) {
-    for (uint64_t e = e0 + threadIdx.x; e < e1; e += kThreads) atomicAdd(&hist[t_key[e]], 1u);
+    for (uint64_t e = e0 + threadIdx.x; e < e1; e += kThreads) add(key[e]);
   } else {
-    for (uint64_t e = e0 + threadIdx.x; e < a0; e += kThreads) atomicAdd(&hist[t_key[e]], 1u);
-    for (uint64_t e = a1 + threadIdx.x; e < e1; e += kThreads) atomicAdd(&hist[t_key[e]], 1u);
-    const uint4* k8 = reinterpret_cast<const uint4*>(t_key + a0);
-    const uint64_t n8 = (a1 - a0) / 8;
+    for (uint64_t e = e0 + threadIdx.x; e < a0; e += kThreads) add(key[e]);
+    for (uint64_t e = a1 + threadIdx.x; e < e1; e += kThreads) add(key[e]);
+    const uint4* kv = reinterpret_cast<const uint4*>(key + a0);
+    const uint64_t nv = (a1 - a0) / kVec;
 #pragma unroll 2
-    for (uint64_t i = threadIdx.x; i < n8; i += kThreads) {
-      const uint4 q = k8[i];
+    for (uint64_t i = threadIdx.x; i < nv; i += kThreads) {
+      const uint4 q = kv[i];
       const uint32_t w[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        atomicAdd(&hist[w[j] & 0xFFFFu], 1u);
-        atomicAdd(&hist[w[j] >> 16], 1u);
+        if constexpr (sizeof(KeyIn) == 2) {
+          add(w[j] & 0xFFFFu);
+          add(w[j] >> 16);
+        } else {
+          add(w[j]);
+        }
       }
     }
   }
@@ -394,40 +427,47 @@ __global__ __launch_bounds__(kThreads) void k_lowkey_hist(const uint16_t* __rest
   for (uint32_t c = threadIdx.x; c < kLow; c += kThreads) out[c] = hist[c];
 }
 
-/*! \brief per bucket: column totals over segments -> col_ptr; per-segment
- *  cursors in H.  Thread t walks columns t, t + 256, ... so every H access of
+/*! \brief digit scan, one workgroup per bucket: digit totals over the
+ *  segments -> the exclusive starts `starts[b * 2^kB + digit]` (absolute
+ *  positions; entries past nstarts are not written: T4's column pointer, L2's
+ *  super-bucket starts) and per-segment cursors in H (u32 offsets from the
+ *  bucket base).  Thread t walks digits t, t + 256, ... so every H access of
  *  a segment row is one coalesced 1 KiB line run (round 4 walked 16
  *  consecutive columns per thread: 64-byte-strided lanes, 354 us); the scan
- *  over the bucket's columns runs on the LDS copy of the totals. */
-template <int kB>
-__global__ __launch_bounds__(kThreads) void k_lowkey_scan(uint32_t* __restrict__ H,
-                                                          const uint64_t* __restrict__ bstart,
-                                                          uint64_t num_features,
-                                                          uint64_t* __restrict__ col_ptr) {
+ *  over the bucket's digits runs on the LDS copy of the totals. */
+template <int kB, int kSeg>
+__global__ __launch_bounds__(kThreads) void k_digit_scan(uint32_t* __restrict__ H,
+                                                         const uint64_t* __restrict__ bstart,
+                                                         uint64_t nstarts,
+                                                         uint64_t* __restrict__ starts) {
   constexpr uint32_t kLow = 1u << kB;
-  __shared__ uint32_t s_tot[kLow];  // column totals, then exclusive column starts (u32)
+  static_assert(kLow % kThreads == 0, "whole digits per thread");
+  __shared__ uint32_t s_tot[kLow];  // digit totals, then exclusive digit starts (u32)
   __shared__ uint64_t swave[kWaves];
-  constexpr uint32_t kPer = kLow / kThreads;  // columns per thread
+  constexpr uint32_t kPer = kLow / kThreads;  // digits per thread
   const uint32_t b = blockIdx.x;
-  uint32_t* Hb = H + static_cast<size_t>(b) * kSegments * kLow;
-  // 1. per column: the segments' counts -> offsets inside the column (in H)
-  //    and the column total (coalesced: consecutive threads, consecutive columns)
+  uint32_t* Hb = H + static_cast<size_t>(b) * kSeg * kLow;
+  // 1. per digit: the segments' counts -> offsets inside the digit's run (in
+  //    H) and the digit total (coalesced: consecutive threads, consecutive
+  //    digits).  All of a digit's counts are loaded before the first offset is
+  //    stored: the loads and stores go to one array, so interleaved the
+  //    compiler keeps them in program order, one memory round trip per segment
 #pragma unroll 4
   for (uint32_t i = 0; i < kPer; ++i) {
     const uint32_t c = i * kThreads + threadIdx.x;
-    uint32_t h[kSegments];
+    uint32_t h[kSeg];
 #pragma unroll
-    for (int s = 0; s < kSegments; ++s) h[s] = Hb[static_cast<size_t>(s) * kLow + c];
+    for (int s = 0; s < kSeg; ++s) h[s] = Hb[static_cast<size_t>(s) * kLow + c];
     uint32_t acc = 0;
 #pragma unroll
-    for (int s = 0; s < kSegments; ++s) {
+    for (int s = 0; s < kSeg; ++s) {
       Hb[static_cast<size_t>(s) * kLow + c] = acc;
       acc += h[s];
     }
     s_tot[c] = acc;
   }
   __syncthreads();
-  // 2. exclusive scan of the 4096 totals: thread t owns columns 16 t .. 16 t + 15
+  // 2. exclusive scan of the totals: thread t owns digits kPer t .. kPer t + kPer - 1
   const uint32_t c0 = threadIdx.x * kPer;
   uint32_t tot[kPer];
   uint64_t sum = 0;
@@ -447,42 +487,60 @@ __global__ __launch_bounds__(kThreads) void k_lowkey_scan(uint32_t* __restrict__
   uint64_t x = before;  // relative to the bucket base (< 2^32: nnz < 2^32)
 #pragma unroll
   for (uint32_t i = 0; i < kPer; ++i) {
-    const uint64_t c = static_cast<uint64_t>(b) * kLow + c0 + i;
-    if (c < num_features) col_ptr[c] = base + x;
-    s_tot[c0 + i] = static_cast<uint32_t>(x);
+    const uint64_t g = static_cast<uint64_t>(b) * kLow + c0 + i;
+    if (g < nstarts) starts[g] = base + x;
+    s_tot[c0 + i] = static_cast<uint32_t>(x);  // (its own digits: no other thread reads them here)
     x += tot[i];
   }
   __syncthreads();
-  // 3. cursors become absolute CSC positions (u32 offsets from the bucket base)
+  // 3. cursors from the bucket base: the digit's start + the segment's offset
 #pragma unroll 4
   for (uint32_t i = 0; i < kPer; ++i) {
     const uint32_t c = i * kThreads + threadIdx.x;
     const uint32_t start = s_tot[c];
 #pragma unroll
-    for (int s = 0; s < kSegments; ++s) Hb[static_cast<size_t>(s) * kLow + c] += start;
+    for (int s = 0; s < kSeg; ++s) Hb[static_cast<size_t>(s) * kLow + c] += start;
   }
 }
 
-
-// kPair: the output is interleaved (row, value) pairs -- one 8-byte store per
-// entry instead of a 4-byte store into each of two arrays (T4c is bound by
-// the output lines its scattered stores touch)
-// kDepth: 64-entry groups per batch (loads a batch ahead; 8: 74 VGPRs -- 4 took 89)
-template <bool kPair, int kB, int kDepth>
-__global__ __launch_bounds__(dev::kWave) void k_lowkey_scatter(
-    const uint16_t* __restrict__ t_key, const uint32_t* __restrict__ t_row,
+/*!
+ * \brief digit scatter, stable: one wave per (bucket, segment), cursors in
+ *  LDS, the segment's entries in order, ranks among equal digits by ballots
+ *  over the digit bits; the (row, value) pair of t_rv (the row of t_row
+ *  without values) moves to bucket base + cursor, and with kKeyOut the key's
+ *  low 8 bits go along (L2).
+ *  kPair: the output is interleaved (row, value) pairs (the pair form of the
+ *  final CSC, or L2's intermediate pair array) -- one 8-byte store per entry
+ *  instead of a 4-byte store into each of two arrays (the scatter is bound by
+ *  the output lines its scattered stores touch); rows (and values, with
+ *  val_out) in arrays of their own otherwise.
+ */
+template <typename KeyIn, int kShift, int kB, int kSeg, bool kPair, bool kKeyOut>
+__global__ __launch_bounds__(dev::kWave) void k_digit_scatter(
+    const KeyIn* __restrict__ key, const uint32_t* __restrict__ t_row,
     const uint2* __restrict__ t_rv, const uint64_t* __restrict__ bstart,
-    const uint32_t* __restrict__ H, uint32_t* __restrict__ row_out, float* __restrict__ val_out) {
+    const uint32_t* __restrict__ H, uint8_t* __restrict__ key_out, uint32_t* __restrict__ row_out,
+    float* __restrict__ val_out, bool pairs_in) {
   constexpr uint32_t kLow = 1u << kB;
+  // Has values (wave-uniform)?  The pass into the CSC (T4, !kKeyOut) reads it
+  // off val_out: the compiler then knows the pointers of that branch valid and
+  // issues a batch's predicated loads in one run.  L2 always writes pairs
+  // (val_out is null) and takes the flag pairs_in, which leaves a branch per
+  // load.  Measured, the two are not interchangeable: the flag costs T4 50 %
+  // at kB = 12 (3 waves per SIMD: 3.5 ms against 2.3 ms), the pointer test
+  // costs L2 2 % at S = 16 (3.21 ms against 3.14 ms)
+  const bool with_values = kKeyOut ? pairs_in : val_out != nullptr;
+  // 64-entry groups per batch (loads a batch ahead; 8: 74 VGPRs in T4 -- 4 took 89)
+  constexpr int kDepth = 8;
   __shared__ uint32_t cur[kLow];
-  const uint32_t b = blockIdx.x / kSegments;
-  const int s = static_cast<int>(blockIdx.x % kSegments);
+  const uint32_t b = blockIdx.x / kSeg;
+  const int s = static_cast<int>(blockIdx.x % kSeg);
   const int lane = dev::lane_id();
   const uint32_t* Hs = H + static_cast<size_t>(blockIdx.x) * kLow;
   for (uint32_t c = lane; c < kLow; c += dev::kWave) cur[c] = Hs[c];
   dev::wave_sync();
   uint64_t e0, e1;
-  segment(bstart, b, s, &e0, &e1);
+  seg_range<kSeg>(bstart, b, s, &e0, &e1);
   const uint64_t base = bstart[b];
   const uint64_t below = lanes_below();
   // The segment walks in batches of kDepth groups of 64 consecutive
@@ -500,8 +558,8 @@ __global__ __launch_bounds__(dev::kWave) void k_lowkey_scatter(
     for (int j = 0; j < kDepth; ++j) {
       const uint64_t e = at + static_cast<uint64_t>(j) * dev::kWave + lane;
       const bool ok = e < e1;
-      x->k[j] = ok ? t_key[e] : 0u;
-      if (val_out != nullptr) {
+      x->k[j] = ok ? static_cast<uint32_t>(key[e]) : 0u;
+      if (with_values) {
         const uint2 rv = ok ? t_rv[e] : make_uint2(0u, 0u);
         x->r[j] = rv.x;
         x->v[j] = __uint_as_float(rv.y);
@@ -518,7 +576,7 @@ __global__ __launch_bounds__(dev::kWave) void k_lowkey_scatter(
 #pragma unroll
     for (int j = 0; j < kDepth; ++j) {
       const bool valid = at + static_cast<uint64_t>(j) * dev::kWave + lane < e1;
-      const uint64_t m = match_lanes(x.k[j], kB, valid);
+      const uint64_t m = match_lanes(digit_of<kShift, kB>(x.k[j]), kB, valid);
       rk[j] = static_cast<uint32_t>(__popcll(m & below)) |
               (static_cast<uint32_t>(__popcll(m)) << 8);
       // one group's ballots at a time: interleaved, the kB ballots of all
@@ -531,19 +589,20 @@ __global__ __launch_bounds__(dev::kWave) void k_lowkey_scatter(
       const uint64_t g = at + static_cast<uint64_t>(j) * dev::kWave;
       if (g >= e1) break;  // wave-uniform
       const bool valid = g + lane < e1;
-      const uint32_t k = x.k[j];
+      const uint32_t d = digit_of<kShift, kB>(x.k[j]);
       const uint32_t rank = rk[j] & 0xFFu, n = rk[j] >> 8;
-      const uint32_t before = valid ? cur[k] : 0u;
+      const uint32_t before = valid ? cur[d] : 0u;
       dev::wave_sync();
       if (valid) {
         const uint64_t pos = base + before + rank;
+        if constexpr (kKeyOut) key_out[pos] = static_cast<uint8_t>(x.k[j] & 0xFFu);
         if constexpr (kPair) {
           reinterpret_cast<uint2*>(row_out)[pos] = make_uint2(x.r[j], __float_as_uint(x.v[j]));
         } else {
           row_out[pos] = x.r[j];
           if (val_out != nullptr) val_out[pos] = x.v[j];
         }
-        if (rank + 1 == n) cur[k] = before + n;
+        if (rank + 1 == n) cur[d] = before + n;
       }
       dev::wave_sync();
     }
@@ -564,215 +623,16 @@ __global__ __launch_bounds__(dev::kWave) void k_lowkey_scatter(
 // Three levels (feature spaces above 2^22, up to 2^28).  T1-T3 split the
 // entries into <= 1024 buckets of 2^S columns (S = 16 .. 18, the low S bits
 // kept as a u32 key); a bucket's 2^S columns are too many for one LDS cursor
-// table, so two more stable counting-sort passes of T4's shape follow:
-//   L2 per (bucket, segment): digit = key >> 8 (2^(S-8) values) -> the
-//      entries in (bucket, mid) "super-bucket" order, the low 8 bits kept as
-//      a u8 key; the super-bucket starts come from L2's scan;
+// table, so two more stable counting-sort passes follow:
+//   L2 the digit pass per (bucket, segment): digit = key >> 8 (2^(S-8)
+//      values) -> the entries in (bucket, mid) "super-bucket" order, the low
+//      8 bits kept as a u8 key; the super-bucket starts come from L2's scan;
 //   L3 per super-bucket (~1500 entries each at 2^26 x 400 M), one wave:
 //      digit = the low 8 bits -> the final CSC position, the column pointer
 //      (k_local_sort256: counts, scan and placement without a global
 //      histogram).
 // Every pass scatters into at most 1024 (L2) / 256 (L3) open runs per wave
-// (T4c's 1024 - 4096 in the two-level sort).
-
-/*! \brief [begin, end) of segment s of kSeg segments of bucket b */
-template <int kSeg>
-__device__ __forceinline__ void seg_range(const uint64_t* __restrict__ bstart, uint32_t b, int s,
-                                          uint64_t* begin, uint64_t* end) {
-  const uint64_t b0 = bstart[b], b1 = bstart[b + 1];
-  const uint64_t n = b1 - b0;
-  *begin = b0 + n * static_cast<uint64_t>(s) / kSeg;
-  *end = b0 + n * static_cast<uint64_t>(s + 1) / kSeg;
-}
-
-/*! \brief L2 / L3 histogram: per (bucket, segment), the digit (key >> kShift)
- *  & (2^kB - 1) of its entries -> H[bucket][segment][2^kB] */
-template <typename KeyIn, int kShift, int kB, int kSeg>
-__global__ __launch_bounds__(kThreads) void k_digit_hist(const KeyIn* __restrict__ key,
-                                                         const uint64_t* __restrict__ bstart,
-                                                         uint32_t* __restrict__ H) {
-  constexpr uint32_t kLow = 1u << kB;
-  __shared__ uint32_t hist[kLow];
-  const uint32_t b = blockIdx.x / kSeg;
-  const int s = static_cast<int>(blockIdx.x % kSeg);
-  for (uint32_t c = threadIdx.x; c < kLow; c += kThreads) hist[c] = 0;
-  __syncthreads();
-  uint64_t e0, e1;
-  seg_range<kSeg>(bstart, b, s, &e0, &e1);
-  auto add = [&](uint32_t k) { atomicAdd(&hist[(k >> kShift) & (kLow - 1u)], 1u); };
-  if constexpr (sizeof(KeyIn) == 4) {
-    // four keys per 16-byte load over the aligned middle of the segment
-    const uint64_t a0 = (e0 + 3) & ~3ull, a1 = e1 & ~3ull;
-    if (a0 < a1) {
-      for (uint64_t e = e0 + threadIdx.x; e < a0; e += kThreads) add(key[e]);
-      for (uint64_t e = a1 + threadIdx.x; e < e1; e += kThreads) add(key[e]);
-      const uint4* k4 = reinterpret_cast<const uint4*>(key + a0);
-      const uint64_t n4 = (a1 - a0) / 4;
-      for (uint64_t i = threadIdx.x; i < n4; i += kThreads) {
-        const uint4 q = k4[i];
-        add(q.x);
-        add(q.y);
-        add(q.z);
-        add(q.w);
-      }
-      e0 = e1;  // done
-    }
-  }
-  for (uint64_t e = e0 + threadIdx.x; e < e1; e += kThreads) add(static_cast<uint32_t>(key[e]));
-  __syncthreads();
-  uint32_t* out = H + static_cast<size_t>(blockIdx.x) * kLow;
-  for (uint32_t c = threadIdx.x; c < kLow; c += kThreads) out[c] = hist[c];
-}
-
-/*! \brief L2 / L3 scan, per bucket: digit totals over the segments -> the
- *  exclusive starts `starts[b * 2^kB + digit]` (absolute positions; entries
- *  past nstarts are not written) and absolute per-segment cursors in H */
-template <int kB, int kSeg>
-__global__ __launch_bounds__(kThreads) void k_digit_scan(uint32_t* __restrict__ H,
-                                                         const uint64_t* __restrict__ bstart,
-                                                         uint64_t nstarts,
-                                                         uint64_t* __restrict__ starts) {
-  constexpr uint32_t kLow = 1u << kB;
-  constexpr uint32_t kPer = (kLow + kThreads - 1) / kThreads;
-  __shared__ uint32_t s_tot[kLow];
-  __shared__ uint64_t swave[kWaves];
-  const uint32_t b = blockIdx.x;
-  uint32_t* Hb = H + static_cast<size_t>(b) * kSeg * kLow;
-  for (uint32_t c = threadIdx.x; c < kLow; c += kThreads) {
-    uint32_t acc = 0;
-#pragma unroll
-    for (int q = 0; q < kSeg; ++q) {
-      const uint32_t h = Hb[static_cast<size_t>(q) * kLow + c];
-      Hb[static_cast<size_t>(q) * kLow + c] = acc;
-      acc += h;
-    }
-    s_tot[c] = acc;
-  }
-  __syncthreads();
-  const uint32_t c0 = threadIdx.x * kPer;
-  uint32_t tot[kPer];
-  uint64_t sum = 0;
-#pragma unroll
-  for (uint32_t i = 0; i < kPer; ++i) {
-    tot[i] = c0 + i < kLow ? s_tot[c0 + i] : 0u;
-    sum += tot[i];
-  }
-  uint64_t wtot;
-  const uint64_t wx = dev::wave_excl_scan(sum, &wtot);
-  const int w = threadIdx.x / dev::kWave;
-  if (dev::lane_id() == 0) swave[w] = wtot;
-  __syncthreads();
-  uint64_t x = wx;
-  for (int q = 0; q < w; ++q) x += swave[q];
-  const uint64_t base = bstart[b];
-  __syncthreads();  // every thread has read s_tot
-#pragma unroll
-  for (uint32_t i = 0; i < kPer; ++i) {
-    const uint32_t c = c0 + i;
-    if (c < kLow) {
-      const uint64_t g = static_cast<uint64_t>(b) * kLow + c;
-      if (g < nstarts) starts[g] = base + x;
-      s_tot[c] = static_cast<uint32_t>(x);
-      x += tot[i];
-    }
-  }
-  __syncthreads();
-  for (uint32_t c = threadIdx.x; c < kLow; c += kThreads) {
-    const uint32_t start = s_tot[c];
-#pragma unroll
-    for (int q = 0; q < kSeg; ++q) Hb[static_cast<size_t>(q) * kLow + c] += start;
-  }
-}
-
-/*!
- * \brief L2 / L3 stable scatter: one wave per (bucket, segment), digit ranks
- *  by ballots as in T4c; the (row, value) pair (or the row) moves to
- *  bucket base + cursor, and with key_out the key's low 8 bits go along (L2).
- *  Output pairs when kPair (row / value arrays of the final CSC, or L2's
- *  intermediate pair array); rows alone otherwise.
- */
-template <typename KeyIn, int kShift, int kB, int kSeg, bool kPair>
-__global__ __launch_bounds__(dev::kWave) void k_digit_scatter(
-    const KeyIn* __restrict__ key, const uint32_t* __restrict__ t_row,
-    const uint2* __restrict__ t_rv, const uint64_t* __restrict__ bstart,
-    const uint32_t* __restrict__ H, uint8_t* __restrict__ key_out, uint32_t* __restrict__ row_out,
-    float* __restrict__ val_out, bool with_values) {
-  constexpr uint32_t kLow = 1u << kB;
-  constexpr int kDepth = 8;
-  __shared__ uint32_t cur[kLow];
-  const uint32_t b = blockIdx.x / kSeg;
-  const int s = static_cast<int>(blockIdx.x % kSeg);
-  const int lane = dev::lane_id();
-  const uint32_t* Hs = H + static_cast<size_t>(blockIdx.x) * kLow;
-  for (uint32_t c = lane; c < kLow; c += dev::kWave) cur[c] = Hs[c];
-  dev::wave_sync();
-  uint64_t e0, e1;
-  seg_range<kSeg>(bstart, b, s, &e0, &e1);
-  const uint64_t base = bstart[b];
-  const uint64_t below = lanes_below();
-  struct Batch {
-    uint32_t k[kDepth], r[kDepth], v[kDepth];
-  };
-  auto load = [&](uint64_t at, Batch* x) {
-#pragma unroll
-    for (int j = 0; j < kDepth; ++j) {
-      const uint64_t e = at + static_cast<uint64_t>(j) * dev::kWave + lane;
-      const bool ok = e < e1;
-      x->k[j] = ok ? static_cast<uint32_t>(key[e]) : 0u;
-      if (with_values) {
-        const uint2 rv = ok ? t_rv[e] : make_uint2(0u, 0u);
-        x->r[j] = rv.x;
-        x->v[j] = rv.y;
-      } else {
-        x->r[j] = ok ? t_row[e] : 0u;
-        x->v[j] = 0u;
-      }
-    }
-  };
-  auto process = [&](uint64_t at, const Batch& x) {
-    uint32_t rk[kDepth];
-#pragma unroll
-    for (int j = 0; j < kDepth; ++j) {
-      const bool valid = at + static_cast<uint64_t>(j) * dev::kWave + lane < e1;
-      const uint64_t m = match_lanes((x.k[j] >> kShift) & (kLow - 1u), kB, valid);
-      rk[j] = static_cast<uint32_t>(__popcll(m & below)) |
-              (static_cast<uint32_t>(__popcll(m)) << 8);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int j = 0; j < kDepth; ++j) {
-      const uint64_t g = at + static_cast<uint64_t>(j) * dev::kWave;
-      if (g >= e1) break;  // wave-uniform
-      const bool valid = g + lane < e1;
-      const uint32_t d = (x.k[j] >> kShift) & (kLow - 1u);
-      const uint32_t rank = rk[j] & 0xFFu, n = rk[j] >> 8;
-      const uint32_t before = valid ? cur[d] : 0u;
-      dev::wave_sync();
-      if (valid) {
-        const uint64_t pos = base + before + rank;  // (cursors: from the bucket base)
-        if (key_out != nullptr) key_out[pos] = static_cast<uint8_t>(x.k[j] & 0xFFu);
-        if constexpr (kPair) {
-          reinterpret_cast<uint2*>(row_out)[pos] = make_uint2(x.r[j], x.v[j]);
-        } else {
-          row_out[pos] = x.r[j];
-          if (val_out != nullptr) val_out[pos] = __uint_as_float(x.v[j]);
-        }
-        if (rank + 1 == n) cur[d] = before + n;
-      }
-      dev::wave_sync();
-    }
-  };
-  constexpr uint64_t kBatch = static_cast<uint64_t>(kDepth) * dev::kWave;
-  Batch A, B;
-  load(e0, &A);
-  for (uint64_t at = e0; at < e1; at += 2 * kBatch) {
-    load(at + kBatch, &B);
-    process(at, A);
-    if (at + kBatch >= e1) break;
-    load(at + 2 * kBatch, &A);
-    process(at + kBatch, B);
-  }
-}
+// (T4's scatter: 1024 - 4096 in the two-level sort).
 
 /*!
  * \brief L3 in one pass over a super-bucket: one wave per super-bucket (4
@@ -884,38 +744,20 @@ struct TransposePlan {
   size_t key2_off, rv2_off, super_off;
 };
 
-constexpr int kL2Seg = 16;  // L2 segments per bucket
 constexpr int kL3Bits = 8;  // L3 digit: the low 8 bits
 constexpr int kMaxBits3 = 18;  // S <= 18: 2^28 features
 
 /*!
  * \brief columns per bucket for a feature space: the narrowest of 2^10 ..
- *  2^12 that keeps the buckets <= kMaxBuckets (DMLC_T_LOWBITS forces a
- *  width that fits).  Narrower buckets shrink T4c's LDS cursor table (more
- *  waves per CU) and its ballots, and widen T3's fan-out.
+ *  2^12 that keeps the buckets <= kMaxBuckets.  Narrower buckets shrink T4's
+ *  LDS cursor table (more waves per CU) and its ballots, and widen T3's
+ *  fan-out.
  */
 int LowBits(uint64_t num_features) {
-  static const int forced = [] {
-    const char* v = std::getenv("DMLC_T_LOWBITS");
-    return v != nullptr ? std::atoi(v) : 0;
-  }();
-  auto fits = [&](int b) { return num_features <= (static_cast<uint64_t>(kMaxBuckets) << b); };
-  if (forced >= kMinLowBits && forced <= kMaxLowBits && fits(forced)) return forced;
-  for (int b = kDefaultLowBits; b < kMaxLowBits; ++b) {
-    if (fits(b)) return b;
+  for (int b = kMinLowBits; b < kMaxLowBits; ++b) {
+    if (num_features <= (static_cast<uint64_t>(kMaxBuckets) << b)) return b;
   }
   return kMaxLowBits;
-}
-
-/*! \brief sub-tiles per T1 / T3 block (DMLC_T_BLOCK_SUBS overrides, 1 .. 64):
- *  fewer blocks shrink G (buckets x blocks, written by T1 column by column) */
-int BlockSubs() {
-  static const int subs = [] {
-    const char* v = std::getenv("DMLC_T_BLOCK_SUBS");
-    const int k = v != nullptr ? std::atoi(v) : 0;
-    return k >= 1 && k <= 64 ? k : kBlockSubs;
-  }();
-  return subs;
 }
 
 TransposePlan Plan(uint64_t nnz, uint64_t num_features) {
@@ -935,7 +777,7 @@ TransposePlan Plan(uint64_t nnz, uint64_t num_features) {
   if (p.nbuckets == 0) p.nbuckets = 1;
   p.bucket_bits = 0;
   while ((1u << p.bucket_bits) < p.nbuckets) ++p.bucket_bits;
-  p.block_elems = static_cast<uint64_t>(BlockSubs()) * kSubElems;
+  p.block_elems = static_cast<uint64_t>(kBlockSubs) * kSubElems;
   p.nblocks = (nnz + p.block_elems - 1) / p.block_elems;
   if (p.nblocks == 0) p.nblocks = 1;
   p.g_words = static_cast<size_t>(p.nbuckets) * p.nblocks + 1;  // + the bucket-end sentinel
@@ -945,7 +787,7 @@ TransposePlan Plan(uint64_t nnz, uint64_t num_features) {
   if (p.three) {
     const uint64_t mid = uint64_t(1) << (p.low_bits - kL3Bits);
     p.nsuper = static_cast<uint64_t>(p.nbuckets) * mid;
-    p.h_words = static_cast<size_t>(p.nbuckets) * kL2Seg * mid;  // (L3 keeps its counts in LDS)
+    p.h_words = static_cast<size_t>(p.nbuckets) * kSegments * mid;  // (L3 keeps its counts in LDS)
   }
   p.nchunks = (nnz + kChunk - 1) / kChunk;
   size_t off = 0;
@@ -985,22 +827,31 @@ __global__ void k_bucket_starts(const uint64_t* __restrict__ G, size_t nblocks, 
   }
 }
 
-/*! \brief T1 .. T4 at 2^kB columns per bucket */
-template <typename IndexType, int kB>
-void RunSort(const TransposePlan& p, const uint64_t* offset, size_t nrows, uint64_t base,
-             uint64_t nnz, const IndexType* index, const float* value, uint64_t num_features,
-             uint64_t* col_ptr, uint32_t* row_out, float* val_out, void* scratch,
-             uint32_t* error, hipStream_t stream) {
+/*! \brief the scratch arrays L1 leaves for the digit passes */
+template <typename KeyT>
+struct Bucketed {
+  KeyT* t_key;       // the low kB bits of every entry's column, in bucket order
+  uint32_t* t_row;   // rows alone (no values), or
+  uint2* t_rv;       // (row, value) pairs over the row + value regions (>= 8 nnz bytes)
+  uint32_t* H;       // room for the digit histograms
+  uint64_t* bstart;  // bucket starts, bstart[nbuckets] = nnz
+};
+
+/*! \brief L1 = T1 + T2 + T3 at 2^kB columns per bucket: the entries in bucket order */
+template <typename IndexType, int kB, typename KeyT>
+Bucketed<KeyT> RunL1(const TransposePlan& p, const uint64_t* offset, size_t nrows, uint64_t base,
+                     uint64_t nnz, const IndexType* index, const float* value,
+                     uint64_t num_features, void* scratch, uint32_t* error, hipStream_t stream) {
   char* sc = static_cast<char*>(scratch);
-  uint16_t* t_key = reinterpret_cast<uint16_t*>(sc + p.key_off);
-  // rows alone, or (row, value) pairs over the row + value regions (>= 8 nnz bytes)
-  uint32_t* t_row = reinterpret_cast<uint32_t*>(sc + p.row_off);
-  uint2* t_rv = reinterpret_cast<uint2*>(sc + p.row_off);
+  Bucketed<KeyT> o;
+  o.t_key = reinterpret_cast<KeyT*>(sc + p.key_off);
+  o.t_row = reinterpret_cast<uint32_t*>(sc + p.row_off);
+  o.t_rv = reinterpret_cast<uint2*>(sc + p.row_off);
+  o.H = reinterpret_cast<uint32_t*>(sc + p.h_off);
+  o.bstart = reinterpret_cast<uint64_t*>(sc + p.total);
   uint64_t* G = reinterpret_cast<uint64_t*>(sc + p.g_off);
   uint64_t* partials = reinterpret_cast<uint64_t*>(sc + p.partials_off);
-  uint32_t* H = reinterpret_cast<uint32_t*>(sc + p.h_off);
   uint32_t* chunk_row = reinterpret_cast<uint32_t*>(sc + p.chunk_off);
-  uint64_t* bstart = reinterpret_cast<uint64_t*>(sc + p.total);
   const IndexType* idx = index + base;  // entries [base, base + nnz) of the arrays
   const float* val = value != nullptr ? value + base : nullptr;
   // T1 + T2
@@ -1011,34 +862,58 @@ void RunSort(const TransposePlan& p, const uint64_t* offset, size_t nrows, uint6
   }
   LaunchScanU64(G, p.g_words, partials, partials + p.partials_words - 1, stream);
   hipLaunchKernelGGL(k_bucket_starts, dim3((p.nbuckets + kThreads) / kThreads), dim3(kThreads), 0,
-                     stream, G, p.nblocks, p.nbuckets, nnz, bstart);
+                     stream, G, p.nblocks, p.nbuckets, nnz, o.bstart);
   // T3
   if (nnz != 0) {
     hipLaunchKernelGGL(k_chunk_rows, dim3((p.nchunks + kThreads - 1) / kThreads), dim3(kThreads),
                        0, stream, offset, nrows, base, nnz, chunk_row);
-    hipLaunchKernelGGL((k_bucket_scatter<IndexType, kB>), dim3(p.nblocks), dim3(kThreads), 0,
+    hipLaunchKernelGGL((k_bucket_scatter<IndexType, kB, KeyT>), dim3(p.nblocks), dim3(kThreads), 0,
                        stream, offset, nrows, base, idx, val, nnz, num_features, p.nbuckets,
-                       p.bucket_bits, G, p.nblocks, p.block_elems, chunk_row, t_key, t_row,
-                       t_rv);
+                       p.bucket_bits, G, p.nblocks, p.block_elems, chunk_row, o.t_key, o.t_row,
+                       o.t_rv);
   }
-  // T4
-  const unsigned nseg = p.nbuckets * kSegments;
-  hipLaunchKernelGGL(k_lowkey_hist<kB>, dim3(nseg), dim3(kThreads), 0, stream, t_key, bstart, H);
-  hipLaunchKernelGGL(k_lowkey_scan<kB>, dim3(p.nbuckets), dim3(kThreads), 0, stream, H, bstart,
-                     num_features, col_ptr);
-  // (row, value) pairs when val_out is the float after row_out (8-byte aligned)
-  const bool paired = val_out != nullptr && val_out == reinterpret_cast<float*>(row_out) + 1;
+  return o;
+}
+
+/*! \brief the final CSC is (row, value) pairs when val_out is the float after
+ *  row_out (8-byte aligned) */
+bool PairedOutput(const uint32_t* row_out, const float* val_out) {
+  const bool paired = val_out != nullptr && val_out == reinterpret_cast<const float*>(row_out) + 1;
   if (paired) {
-    CHECK_EQ(reinterpret_cast<uintptr_t>(row_out) & 7u, 0u) << "transpose: pair output not 8-byte aligned";
-    hipLaunchKernelGGL((k_lowkey_scatter<true, kB, 8>), dim3(nseg), dim3(dev::kWave), 0, stream,
-                       t_key, t_row, t_rv, bstart, H, row_out, val_out);
-  } else {
-    hipLaunchKernelGGL((k_lowkey_scatter<false, kB, 8>), dim3(nseg), dim3(dev::kWave), 0, stream,
-                       t_key, t_row, t_rv, bstart, H, row_out, val_out);
+    CHECK_EQ(reinterpret_cast<uintptr_t>(row_out) & 7u, 0u)
+        << "transpose: pair output not 8-byte aligned";
   }
-  hipLaunchKernelGGL(k_transpose_close, dim3(1), dim3(1), 0, stream, bstart, p.nbuckets,
+  return paired;
+}
+
+/*! \brief T1 .. T4 at 2^kB columns per bucket */
+template <typename IndexType, int kB>
+void RunSort(const TransposePlan& p, const uint64_t* offset, size_t nrows, uint64_t base,
+             uint64_t nnz, const IndexType* index, const float* value, uint64_t num_features,
+             uint64_t* col_ptr, uint32_t* row_out, float* val_out, void* scratch,
+             uint32_t* error, hipStream_t stream) {
+  const Bucketed<uint16_t> l1 = RunL1<IndexType, kB, uint16_t>(
+      p, offset, nrows, base, nnz, index, value, num_features, scratch, error, stream);
+  // T4: the digit pass over the whole low key -> the CSC and its column pointer
+  const unsigned nseg = p.nbuckets * kSegments;
+  hipLaunchKernelGGL((k_digit_hist<uint16_t, 0, kB, kSegments>), dim3(nseg), dim3(kThreads), 0,
+                     stream, l1.t_key, l1.bstart, l1.H);
+  hipLaunchKernelGGL((k_digit_scan<kB, kSegments>), dim3(p.nbuckets), dim3(kThreads), 0, stream,
+                     l1.H, l1.bstart, num_features, col_ptr);
+  const bool with_values = val_out != nullptr;
+  if (PairedOutput(row_out, val_out)) {
+    hipLaunchKernelGGL((k_digit_scatter<uint16_t, 0, kB, kSegments, true, false>), dim3(nseg),
+                       dim3(dev::kWave), 0, stream, l1.t_key, l1.t_row, l1.t_rv, l1.bstart, l1.H,
+                       nullptr, row_out, val_out, with_values);
+  } else {
+    hipLaunchKernelGGL((k_digit_scatter<uint16_t, 0, kB, kSegments, false, false>), dim3(nseg),
+                       dim3(dev::kWave), 0, stream, l1.t_key, l1.t_row, l1.t_rv, l1.bstart, l1.H,
+                       nullptr, row_out, val_out, with_values);
+  }
+  hipLaunchKernelGGL(k_transpose_close, dim3(1), dim3(1), 0, stream, l1.bstart, p.nbuckets,
                      num_features, col_ptr);
 }
+
 /*! \brief the three-level sort (feature spaces above 2^22): T1-T3 into
  *  buckets of 2^S columns with u32 keys, L2 into super-buckets of 256
  *  columns, L3 into the CSC */
@@ -1048,62 +923,30 @@ void RunSort3(const TransposePlan& p, const uint64_t* offset, size_t nrows, uint
               uint64_t* col_ptr, uint32_t* row_out, float* val_out, void* scratch,
               uint32_t* error, hipStream_t stream) {
   constexpr int kMid = kS - kL3Bits;  // L2 digit bits
+  const Bucketed<uint32_t> l1 = RunL1<IndexType, kS, uint32_t>(
+      p, offset, nrows, base, nnz, index, value, num_features, scratch, error, stream);
   char* sc = static_cast<char*>(scratch);
-  uint32_t* t_key = reinterpret_cast<uint32_t*>(sc + p.key_off);
-  uint32_t* t_row = reinterpret_cast<uint32_t*>(sc + p.row_off);
-  uint2* t_rv = reinterpret_cast<uint2*>(sc + p.row_off);
-  uint64_t* G = reinterpret_cast<uint64_t*>(sc + p.g_off);
-  uint64_t* partials = reinterpret_cast<uint64_t*>(sc + p.partials_off);
-  uint32_t* H = reinterpret_cast<uint32_t*>(sc + p.h_off);
-  uint32_t* chunk_row = reinterpret_cast<uint32_t*>(sc + p.chunk_off);
   uint8_t* t_key2 = reinterpret_cast<uint8_t*>(sc + p.key2_off);
   uint2* t_rv2 = reinterpret_cast<uint2*>(sc + p.rv2_off);
-  uint32_t* t_row2 = reinterpret_cast<uint32_t*>(sc + p.rv2_off);
   uint64_t* sstart = reinterpret_cast<uint64_t*>(sc + p.super_off);
-  uint64_t* bstart = reinterpret_cast<uint64_t*>(sc + p.total);
-  const IndexType* idx = index + base;
-  const float* val = value != nullptr ? value + base : nullptr;
-  const bool with_values = value != nullptr;
-  // L1 = T1 + T2 + T3 at 2^kS columns per bucket (u32 keys)
-  DMLC_HIP_CHECK(hipMemsetAsync(G, 0, p.g_words * sizeof(uint64_t), stream));
-  if (nnz != 0) {
-    hipLaunchKernelGGL((k_bucket_hist<IndexType, kS>), dim3(p.nblocks), dim3(kThreads), 0, stream,
-                       idx, nnz, num_features, p.nbuckets, G, p.nblocks, p.block_elems, error);
-  }
-  LaunchScanU64(G, p.g_words, partials, partials + p.partials_words - 1, stream);
-  hipLaunchKernelGGL(k_bucket_starts, dim3((p.nbuckets + kThreads) / kThreads), dim3(kThreads), 0,
-                     stream, G, p.nblocks, p.nbuckets, nnz, bstart);
-  if (nnz != 0) {
-    hipLaunchKernelGGL(k_chunk_rows, dim3((p.nchunks + kThreads - 1) / kThreads), dim3(kThreads),
-                       0, stream, offset, nrows, base, nnz, chunk_row);
-    hipLaunchKernelGGL((k_bucket_scatter<IndexType, kS, uint32_t>), dim3(p.nblocks),
-                       dim3(kThreads), 0, stream, offset, nrows, base, idx, val, nnz,
-                       num_features, p.nbuckets, p.bucket_bits, G, p.nblocks, p.block_elems,
-                       chunk_row, t_key, t_row, t_rv);
-  }
-  // L2: per (bucket, segment), digit = key >> 8 -> super-bucket order
-  const unsigned n2 = p.nbuckets * kL2Seg;
-  hipLaunchKernelGGL((k_digit_hist<uint32_t, kL3Bits, kMid, kL2Seg>), dim3(n2), dim3(kThreads), 0,
-                     stream, t_key, bstart, H);
-  hipLaunchKernelGGL((k_digit_scan<kMid, kL2Seg>), dim3(p.nbuckets), dim3(kThreads), 0, stream, H,
-                     bstart, p.nsuper, sstart);
+  // L2: the digit pass at digit = key >> 8 -> super-bucket order
+  const unsigned n2 = p.nbuckets * kSegments;
+  hipLaunchKernelGGL((k_digit_hist<uint32_t, kL3Bits, kMid, kSegments>), dim3(n2), dim3(kThreads),
+                     0, stream, l1.t_key, l1.bstart, l1.H);
+  hipLaunchKernelGGL((k_digit_scan<kMid, kSegments>), dim3(p.nbuckets), dim3(kThreads), 0, stream,
+                     l1.H, l1.bstart, p.nsuper, sstart);
   hipLaunchKernelGGL(k_starts_close, dim3(1), dim3(1), 0, stream, sstart, p.nsuper, nnz);
   // (L2 always writes (row, value) pairs -- (row, 0) without values -- which L3 reads)
-  hipLaunchKernelGGL((k_digit_scatter<uint32_t, kL3Bits, kMid, kL2Seg, true>), dim3(n2),
-                     dim3(dev::kWave), 0, stream, t_key, t_row, t_rv, bstart, H, t_key2,
-                     with_values ? reinterpret_cast<uint32_t*>(t_rv2) : t_row2, nullptr,
-                     with_values);
+  hipLaunchKernelGGL((k_digit_scatter<uint32_t, kL3Bits, kMid, kSegments, true, true>), dim3(n2),
+                     dim3(dev::kWave), 0, stream, l1.t_key, l1.t_row, l1.t_rv, l1.bstart,
+                     l1.H, t_key2, reinterpret_cast<uint32_t*>(t_rv2), nullptr, value != nullptr);
   // L3: one wave per super-bucket sorts it by the low 8 bits into the CSC
   // (counts, column pointer and placement in one kernel)
-  const bool paired = val_out != nullptr && val_out == reinterpret_cast<float*>(row_out) + 1;
-  if (paired) {
-    CHECK_EQ(reinterpret_cast<uintptr_t>(row_out) & 7u, 0u) << "transpose: pair output not 8-byte aligned";
-  }
-  (void)t_row2;
+  const bool paired = PairedOutput(row_out, val_out);
   hipLaunchKernelGGL(k_local_sort256, dim3(static_cast<unsigned>((p.nsuper + kWaves - 1) / kWaves)),
                      dim3(kThreads), 0, stream, t_key2, t_rv2, sstart, p.nsuper, num_features,
                      col_ptr, row_out, val_out, paired);
-  hipLaunchKernelGGL(k_transpose_close, dim3(1), dim3(1), 0, stream, bstart, p.nbuckets,
+  hipLaunchKernelGGL(k_transpose_close, dim3(1), dim3(1), 0, stream, l1.bstart, p.nbuckets,
                      num_features, col_ptr);
 }
 }  // namespace

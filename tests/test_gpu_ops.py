@@ -226,14 +226,22 @@ def test_cached_transpose_follows_the_dict_tensors(csr_t):
     torch.testing.assert_close(m.weight.grad, ref.weight.grad, rtol=1e-4, atol=1e-6)
 
 
-def _ref_transpose(t, nfeat):
+def _ref_transpose(t, nfeat, device_ptr=False):
+    """numpy's stable argsort CSC of a device CSR.  device_ptr: the column
+    pointer as a device tensor from torch.bincount (the host searchsorted over
+    2^27 + 1 columns alone takes seconds)"""
+    import torch
     off = t["offset"].cpu().numpy().astype(np.int64)
     lo, hi = off[0], off[-1]
     idx = t["index"].cpu().numpy().astype(np.int64)[lo:hi]
     val = t["value"].cpu().numpy()[lo:hi]
     rows = np.repeat(np.arange(len(off) - 1), np.diff(off))
     order = np.argsort(idx, kind="stable")  # stable: rows ascending within a column
-    ptr = np.searchsorted(idx[order], np.arange(nfeat + 1))
+    if device_ptr:
+        ptr = torch.zeros(nfeat + 1, dtype=torch.int64, device="cuda")
+        ptr[1:] = torch.bincount(t["index"][lo:hi].long(), minlength=nfeat).cumsum(0)
+    else:
+        ptr = np.searchsorted(idx[order], np.arange(nfeat + 1))
     return ptr, rows[order].astype(np.int32), val[order]
 
 
@@ -241,20 +249,32 @@ def _ref_transpose(t, nfeat):
                                                   (70000, 5000, True), (1, 50, False),
                                                   ((1 << 22) + 1, 20000, False),
                                                   (1 << 24, 20000, False), (1 << 26, 20000, False),
-                                                  (1 << 26, 5000, True)])
+                                                  (1 << 26, 5000, True),
+                                                  (1 << 21, 20000, False),
+                                                  (1 << 27, 5000, False),
+                                                  (3, 20000, False)])
 def test_transpose_kernel_is_a_stable_csc(tmp_path, nfeat, rows, index64):
     """the HIP counting-sort transpose equals numpy's stable argsort CSC
     exactly (row ids ascending within every column, values moved with them),
     across bucket counts (1 .. 1024 buckets of 1024 - 4096 columns), the
     three-level sort of wider feature spaces (2^22 + 1 .. 2^26 columns:
     buckets of 2^16 .. 2^18 columns, 256-column super-buckets), 64-bit
-    indices, and a single column"""
+    indices, a single column, and three columns (one bucket of ~400 k entries:
+    segments of many 512-entry batches, up to 64 equal keys per ballot group,
+    segment ends unaligned for the vector histogram).  Bucket widths covered:
+    2^10, 2^11, 2^12 (two levels), 2^16, 2^17 (three; 2^18 would need a 2 GiB
+    column pointer)"""
+    import torch
     p = str(tmp_path / "t.libsvm")
     data.write_synthetic(p, 0, rows, seed=5, num_features=nfeat, min_nnz=1, max_nnz=40)
     t = data.csr_to_torch(data.GPUParser(p, index64=index64).parse_all(data.DeviceCSR(index64)))
     tt = ops.transpose(t, nfeat)
-    ptr, r, v = _ref_transpose(t, nfeat)
-    np.testing.assert_array_equal(tt["offset"].cpu().numpy(), ptr)
+    big = nfeat > 1 << 26  # the column pointer compared on the device
+    ptr, r, v = _ref_transpose(t, nfeat, device_ptr=big)
+    if big:
+        assert tt["offset"].dtype == ptr.dtype and torch.equal(tt["offset"], ptr)
+    else:
+        np.testing.assert_array_equal(tt["offset"].cpu().numpy(), ptr)
     np.testing.assert_array_equal(tt["index"].cpu().numpy(), r)
     np.testing.assert_array_equal(tt["value"].cpu().numpy(), v)
     # values: index / value are the columns of one interleaved pair buffer

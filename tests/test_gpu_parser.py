@@ -600,3 +600,74 @@ def test_extended_number_decoder_edge_values(tmp_path):
     g = data.GPUParser(p, chunk_bytes=4096)
     assert_same(pyref.concat_blocks([g.parse_all().to_host()]), cpu_rows(p, "libsvm"))
     assert g.stats()["exact_chunks"] == 0
+
+
+def test_experiment_variables_are_ignored_by_a_production_build(tmp_path):
+    """The kernels' pricing experiments and retired tuning overrides do not
+    exist outside a -DDMLC_PRICING build: with DMLC_CSV_EXP / DMLC_REC_EXP /
+    DMLC_FILL_EXP (values that skip stores and copies where they are honoured)
+    and DMLC_CSV_POSCOUNT set, a CSV with label and weight columns (the general
+    k_csv_tile_fill), a LibSVM file and a RecordIO shard (HBM replay, counted
+    and one pass) still equal the CPU results exactly.  DMLC_T_LOWBITS and
+    DMLC_T_BLOCK_SUBS are set as well, but no transpose runs here: nothing in
+    src/ reads them any more, which is all that this test can say of them.
+    In a subprocess: such variables are read once."""
+    import json
+    import subprocess
+    import sys
+    from dmlc_core_amd import io
+    csv = str(tmp_path / "e.csv")
+    data.write_synthetic(csv, 0, 2000, format="csv", seed=31)
+    csv_uri = csv + "?label_column=0&weight_column=1"
+    svm = str(tmp_path / "e.libsvm")
+    data.write_synthetic(svm, 0, 2000, format="libsvm", seed=32)
+    rec = str(tmp_path / "e.rec")
+    rng = np.random.default_rng(33)
+    recs = [rng.integers(0, 256, size=int(n), dtype=np.uint8).tobytes()
+            for n in rng.integers(0, 3000, size=300)]
+    w = io.RecordIOWriter(rec)
+    for r in recs:
+        w.write(r)
+    w.close()
+    code = (
+        "import json, sys\n"
+        "import numpy as np\n"
+        "from dmlc_core_amd import data, io\n"
+        "csv_uri, svm, rec, out = sys.argv[1:5]\n"
+        "def save(name, h):\n"
+        "    np.savez(out + name, **{k: v for k, v in h.items() if v is not None})\n"
+        "save('csv', data.GPUParser(csv_uri, format='csv', chunk_bytes=64 * 1024, label_column=0,\n"
+        "                           weight_column=1).parse_all().to_host())\n"
+        "save('svm', data.GPUParser(svm, format='libsvm', chunk_bytes=64 * 1024).parse_all().to_host())\n"
+        "got = {}\n"
+        "for one in (0, 1):\n"
+        "    r = io.GPURecordIO(rec, 0, 1, chunk_bytes=16 * 1024, hbm_cache=1, one_pass=one)\n"
+        "    for e in range(2):\n"
+        "        if e:\n"
+        "            r.before_first()\n"
+        "        r.read_all()\n"
+        "    got[str(one)] = [x.hex() for x in io.split_records(*r.resident_to_host())]\n"
+        "    got['one_pass_chunks' + str(one)] = r.stats()['one_pass_chunks']\n"
+        "print(json.dumps(got))\n")
+    env = dict(os.environ, DMLC_CSV_EXP="2", DMLC_REC_EXP="2", DMLC_FILL_EXP="3",
+               DMLC_CSV_POSCOUNT="0", DMLC_T_LOWBITS="12", DMLC_T_BLOCK_SUBS="30")
+    out = str(tmp_path / "gpu_")
+    res = subprocess.run([sys.executable, "-c", code, csv_uri, svm, rec, out], capture_output=True,
+                         text=True, env=env, timeout=120)
+    assert res.returncode == 0, res.stderr[-3000:]
+
+    def load(name):
+        z = np.load(out + name + ".npz")
+        keys = ("label", "weight", "qid", "offset", "index", "value", "field")
+        return pyref.concat_blocks([{k: z[k] if k in z.files else None for k in keys}])
+
+    c = cpu_rows(csv_uri, "csv")
+    assert len(c["label"]) == 2000 and len(c["index"]) > 0
+    assert_same(load("csv"), c)
+    assert_same(load("svm"), cpu_rows(svm, "libsvm"))
+    got = json.loads(res.stdout.strip().splitlines()[-1])
+    cpu_recs = list(io.iter_records(rec, 0, 1, "recordio"))
+    assert cpu_recs == recs
+    for one in ("0", "1"):
+        assert [bytes.fromhex(x) for x in got[one]] == cpu_recs, one
+    assert got["one_pass_chunks1"] > 0 and got["one_pass_chunks0"] == 0
