@@ -94,7 +94,9 @@ class GPUParser:
     ``delimiter``.  ``packed_h2d`` ("auto" | 0 | 1): send chunks over PCIe as
     4-bit codes packed by ``read_threads`` host threads and expand them on the
     GPU (zero-copy source only; ``stats()`` reports ``packed_chunks``,
-    ``raw_chunks``, ``link_bytes``).  URI ``?k=v`` arguments override them.
+    ``raw_chunks``, ``link_bytes``, ``head_packed``).  ``copy_streams`` (1 |
+    2) and ``pack_head`` (0 | 1): see ``doc/gpu_ingestion.md``.  URI ``?k=v``
+    arguments override them.
     """
 
     def __init__(self, uri: str, part: int = 0, nparts: int = 1, format: str = "libsvm",  # noqa: A002

@@ -100,6 +100,20 @@ struct DeviceParserConfig {
    */
   bool pack_wait{false};
   /*!
+   * \brief packed H2D: once the source has handed in the last piece of a pass,
+   *  queue the first pieces of the next pass to the pack pool, so that a pass
+   *  that follows a rewind starts packed instead of with one raw chunk
+   *  (`?pack_head=0`: off; src/gpu/chunk_feed.h for when it applies)
+   */
+  bool pack_head{true};
+  /*!
+   * \brief H2D copy streams of the chunk transport, 1 or 2 (`?copy_streams=`):
+   *  with 2, chunk n of a pass is copied on stream n & 1, so a chunk's copy is
+   *  already dispatched when the one before it ends (one stream with hbm_cache,
+   *  where only the first pass is copied)
+   */
+  int copy_streams{2};
+  /*!
    * \brief zero-copy pinning: partitions up to zc_pin_budget bytes are
    *  registered whole, larger ones in sliding windows of zc_window_bytes (at
    *  most two pinned, the next prepared in the background)
@@ -146,7 +160,8 @@ struct DeviceParserConfig {
   int shuffle_seed{0};
   /*! \brief apply `?k=v` overrides (chunk_mb, pinned_slots, device_slots,
    *  read_threads, device, format, label_column, weight_column, delimiter,
-   *  fast_path, one_pass, prelaunch, zero_copy, packed_h2d, pack_wait, zc_pin_budget_mb,
+   *  fast_path, one_pass, prelaunch, zero_copy, packed_h2d, pack_wait, pack_head,
+   *  copy_streams, zc_pin_budget_mb,
    *  zc_window_mb, hbm_cache, replay_chunk_mb, replay_first_mb,
    *  shuffle_parts, shuffle_seed) */
   void Update(const std::map<std::string, std::string>& args);
@@ -204,6 +219,9 @@ struct DeviceParserStats {
   /*! \brief packed H2D: chunks sent as 4-bit codes / sent raw, bytes that
    *  crossed the link, exception blocks sent with packed chunks */
   size_t packed_chunks{0}, raw_chunks{0}, link_bytes{0}, exception_blocks{0};
+  /*! \brief packed H2D: passes whose first piece was packed before the pass
+   *  began (cfg.pack_head) and was submitted packed */
+  size_t head_packed{0};
   /*! \brief packed H2D: wall seconds the pack pool had a job open, seconds the
    *  submitting thread waited for a pack, and the part of those waits that
    *  began with no copy outstanding (link time lost to the pool) */

@@ -45,14 +45,18 @@ ChunkFeed::ChunkFeed(const std::string& uri, unsigned part, unsigned nparts,
     order_ = EpochOrder(part, nparts, 1, cfg_.shuffle_seed, {split_->ShardSegments()});
     reader_.reset(new io::ShardReader(split_.get(), cfg_.read_threads));
   }
-  copy_.reset(new Stream());
+  // with hbm_cache only the first pass crosses the link, and the replay's
+  // prelaunch stream is the process's fifth: a second copy stream beside it
+  // measured 1,914 -> 1,537 M rows/s on the replay (profiles/link_idle)
+  ncopy_ = (cfg_.copy_streams == 1 || cfg_.hbm_cache) ? 1 : 2;
+  for (size_t s = 0; s < ncopy_; ++s) copy_[s].reset(new Stream());
+  zeroed_.reset(new Event());
   for (int d = 0; d < cfg_.device_slots; ++d) {
     dtext_.emplace_back(new DeviceBuffer(cfg_.chunk_bytes + kTextPadBytes));
     // the pad is read (never used) by 16-byte loads past the chunk end.  The
-    // memsets go on the copy stream: the streams are non-blocking, so a
+    // memsets go on a copy stream: the streams are non-blocking, so a
     // null-stream hipMemset is not ordered before the H2D copy into the slot
-    DMLC_HIP_CHECK(hipMemsetAsync(dtext_.back()->get(), 0, cfg_.chunk_bytes + kTextPadBytes,
-                                  copy_->get()));
+    MemsetOrdered(dtext_.back()->get(), cfg_.chunk_bytes + kTextPadBytes);
     copied_.emplace_back(new Event());
     parsed_.emplace_back(new Event());
     parsed_.back()->Record(compute_);
@@ -65,7 +69,7 @@ ChunkFeed::ChunkFeed(const std::string& uri, unsigned part, unsigned nparts,
     // point into it, no pool thread may still read it and no DMA may
     zc_->SetDrain([this]() {
       RescueLookahead();
-      copy_->Synchronize();
+      SyncCopyStreams();
     });
     stats_->zc_pin_budget = ZeroCopySource::ShardPinBudget(cfg_.zc_pin_budget);
     if (!zc_->Init(split_.get(), cfg_.chunk_bytes, stats_->zc_pin_budget, cfg_.zc_window_bytes,
@@ -90,7 +94,9 @@ ChunkFeed::ChunkFeed(const std::string& uri, unsigned part, unsigned nparts,
 ChunkFeed::~ChunkFeed() {
   // make sure no transfer still reads a pinned slot we are about to free;
   // destructors never throw, so errors are ignored here
-  if (copy_) (void)hipStreamSynchronize(copy_->get());
+  for (auto& s : copy_) {
+    if (s) (void)hipStreamSynchronize(s->get());
+  }
   if (unpack_) (void)hipStreamSynchronize(unpack_->get());
   (void)hipStreamSynchronize(compute_);
   for (auto& f : inflight_) {
@@ -102,7 +108,22 @@ ChunkFeed::~ChunkFeed() {
   zc_.reset();
 }
 
+/*! \brief every copy queued so far is done */
+void ChunkFeed::SyncCopyStreams() const {
+  for (size_t s = 0; s < ncopy_; ++s) copy_[s]->Synchronize();
+}
+
+/*! \brief zero device memory before the first copy into it, whichever copy
+ *  stream that copy runs on (rare: construction, a regrown slot, the arena) */
+void ChunkFeed::MemsetOrdered(void* ptr, size_t bytes) {
+  DMLC_HIP_CHECK(hipMemsetAsync(ptr, 0, bytes, copy_[0]->get()));
+  if (ncopy_ < 2) return;
+  zeroed_->Record(copy_[0]->get());
+  DMLC_HIP_CHECK(hipStreamWaitEvent(copy_[1]->get(), zeroed_->get(), 0));
+}
+
 bool ChunkFeed::SetEpoch(unsigned e) {
+  if (head_) DropLookahead();  // only a plain rewind adopts head jobs
   if (!order_.shuffled()) return Seek(0);
   DrainInflight();
   order_.Apply(e);
@@ -119,7 +140,14 @@ bool ChunkFeed::Seek(size_t cursor) {
   // a replay restarting at 0 keeps the next epoch's first count, prelaunched
   // beside the last fill (NextEpochFirst; dropped if the chunk differs)
   const bool keep_prelaunch = cursor == 0 && cache_complete_ && !order_.shuffled();
-  DrainInflight();
+  // a rewind after a whole pass: this user runs pass after pass (QueueHeadJobs)
+  if (cursor == 0 && reader_done_ && inflight_.empty() && busy_ == 0 && cursor_ != 0 &&
+      cursor_ == PartitionBytes()) {
+    head_armed_ = true;
+  }
+  // head jobs become this pass's lookahead: the source's cursor is after them
+  const bool adopt = head_ && cursor == 0 && !(cfg_.hbm_cache && cache_complete_);
+  DrainInflight(/*keep_head=*/adopt);
   replay_ = false;
   caching_ = false;
   if (cfg_.hbm_cache) {
@@ -142,7 +170,7 @@ bool ChunkFeed::Seek(size_t cursor) {
     }
   }
   if (zc_ != nullptr) {
-    zc_->Seek(cursor);
+    if (!adopt) zc_->Seek(cursor);
   } else {
     seek_pos_ = cursor;
     iter_.BeforeFirst();
@@ -266,6 +294,7 @@ void ChunkFeed::FillPipeline() {
     if (!NextPiece(&p)) {
       reader_done_ = true;
       if (caching_) cache_complete_ = true;
+      QueueHeadJobs();
       break;
     }
     const PackJob* job = p.job.get();
@@ -277,11 +306,15 @@ void ChunkFeed::FillPipeline() {
       // slot once the parse that last used it has finished
       parsed_[d]->Synchronize();
       dtext_[d].reset(new DeviceBuffer(size + kTextPadBytes));
-      DMLC_HIP_CHECK(hipMemsetAsync(dtext_[d]->get(), 0, size + kTextPadBytes, copy_->get()));
+      MemsetOrdered(dtext_[d]->get(), size + kTextPadBytes);
     }
     char* dst = dtext_[d]->get<char>();
     if (caching_) dst = arena_->get<char>() + CacheChunk(p);
-    DMLC_HIP_CHECK(hipStreamWaitEvent(copy_->get(), parsed_[d]->get(), 0));
+    // consecutive chunks alternate over the copy streams; the slot's events
+    // carry every dependency of this copy
+    const size_t cs = pass_chunks_++ % ncopy_;
+    hipStream_t copy = copy_[cs]->get();
+    DMLC_HIP_CHECK(hipStreamWaitEvent(copy, parsed_[d]->get(), 0));
     int pack_slot = -1;
     const bool packed = job != nullptr && job->state.load() == PackJob::kPacked;
     if (packed) {
@@ -294,21 +327,22 @@ void ChunkFeed::FillPipeline() {
         stats_->unpack_staging_bytes += dstage_[d]->bytes();
       }
       DMLC_HIP_CHECK(hipMemcpyAsync(dstage_[d]->get(), job->out, job->packed_bytes,
-                                    hipMemcpyHostToDevice, copy_->get()));
+                                    hipMemcpyHostToDevice, copy));
       // expanded as soon as the codes have landed, on a stream of its own:
       // the copy stream goes straight on to the next DMA, the compute
       // stream is not held up behind a copy, and the text (the HBM-cache
       // arena's too) is whole even if the chunk is never parsed
-      copied_[d]->Record(copy_->get());
+      copied_[d]->Record(copy);
       DMLC_HIP_CHECK(hipStreamWaitEvent(unpack_->get(), copied_[d]->get(), 0));
       LaunchUnpackText(dstage_[d]->get(), size, job->nexc, alphabet_, dst, unpack_->get());
       unpacked_[d]->Record(unpack_->get());
       pack_slot = job->slot;
       stats_->packed_chunks += 1;
+      if (job->head && job->seq == 0) stats_->head_packed += 1;
       stats_->exception_blocks += job->nexc;
       stats_->link_bytes += job->packed_bytes;
     } else {
-      DMLC_HIP_CHECK(hipMemcpyAsync(dst, p.src, size, hipMemcpyHostToDevice, copy_->get()));
+      DMLC_HIP_CHECK(hipMemcpyAsync(dst, p.src, size, hipMemcpyHostToDevice, copy));
       stats_->raw_chunks += 1;
       stats_->link_bytes += size;
       // a rescued piece is read from its pack slot until the copy is done
@@ -319,9 +353,9 @@ void ChunkFeed::FillPipeline() {
           free_pack_slots_.push_back(job->slot);
         }
       }
-      copied_[d]->Record(copy_->get());
+      copied_[d]->Record(copy);
     }
-    last_copy_d_ = d;
+    last_copy_d_[cs] = d;
     inflight_.push_back(Inflight{p.slot, d, size, p.end_pos, dst, pack_slot, packed});
   }
 }
@@ -347,15 +381,19 @@ size_t ChunkFeed::PackSlotBytes(size_t n, bool may_hold_raw) const {
   return std::max<size_t>(may_hold_raw ? std::max(packed, n) : packed, 4096);
 }
 
-/*! \brief an H2D copy queued earlier in this pass is still outstanding */
-bool ChunkFeed::LinkBusy() const { return last_copy_d_ >= 0 && !copied_[last_copy_d_]->Query(); }
+/*! \brief an H2D copy queued earlier in this pass, on either copy stream, is
+ *  still outstanding */
+bool ChunkFeed::LinkBusy() const {
+  for (size_t s = 0; s < ncopy_; ++s) {
+    if (last_copy_d_[s] >= 0 && !copied_[last_copy_d_[s]]->Query()) return true;
+  }
+  return false;
+}
 
-/*! \brief fetch pieces until the lookahead is full, hand them to the pool and
- *  decide what becomes of the piece at the submit cursor (DecideSubmit).
- *  false: it is left to the pool while the link has work (try again at the
- *  next call); true: NextPackJob carries the decision out */
-bool ChunkFeed::PreparePackJob() {
-  while (!la_end_ && la_.size() < kPackLookahead) {
+/*! \brief fetch pieces from the source until the lookahead holds `limit`,
+ *  each with a pack slot of its own */
+void ChunkFeed::FetchLookahead(size_t limit, bool head) {
+  while (!la_end_ && la_.size() < limit) {
     ZeroCopySource::Piece piece;
     if (!zc_->Next(&piece)) {
       la_end_ = true;
@@ -367,6 +405,7 @@ bool ChunkFeed::PreparePackJob() {
     job->end_pos = zc_->Tell();
     if (piece.size != 0) job->last = piece.ptr[piece.size - 1];
     job->seq = la_seq_++;
+    job->head = head;
     CHECK(!free_pack_slots_.empty()) << "internal error: no free pack slot";
     job->slot = free_pack_slots_.back();
     free_pack_slots_.pop_back();
@@ -377,6 +416,38 @@ bool ChunkFeed::PreparePackJob() {
     job->out = buf.get<uint8_t>();
     la_.push_back(std::move(job));
   }
+}
+
+/*!
+ * \brief the source has handed in the last piece of this pass and the pool
+ *  has nothing left to do: let it pack the first pieces of the next pass (same
+ *  order), which Seek(0) adopts as that pass's lookahead.  The in-flight tail
+ *  of this pass holds up to device_slots pack slots and the lookahead none, so
+ *  kHeadJobs <= kPackLookahead slots are free.
+ */
+void ChunkFeed::QueueHeadJobs() {
+  if (pool_ == nullptr || !cfg_.pack_head || !head_armed_ || cfg_.pack_wait ||
+      cfg_.shuffle_parts > 1 || zc_->windowed() || (cfg_.hbm_cache && cache_complete_)) {
+    return;
+  }
+  CHECK(la_.empty()) << "internal error: lookahead left at the end of a pass";
+  // every job of this pass is settled: the pool's cursor restarts with the
+  // source's, as in DropLookahead (retained windows stay mapped)
+  la_seq_ = submitted_ = la_pushed_ = 0;
+  la_end_ = front_unpushed_ = false;
+  pool_->SetSubmitted(0);
+  zc_->Seek(0);
+  FetchLookahead(kHeadJobs, /*head=*/true);
+  for (; la_pushed_ < la_.size(); ++la_pushed_) pool_->Push(la_[la_pushed_].get());
+  head_ = true;
+}
+
+/*! \brief fetch pieces until the lookahead is full, hand them to the pool and
+ *  decide what becomes of the piece at the submit cursor (DecideSubmit).
+ *  false: it is left to the pool while the link has work (try again at the
+ *  next call); true: NextPackJob carries the decision out */
+bool ChunkFeed::PreparePackJob() {
+  FetchLookahead(kPackLookahead, /*head=*/false);
   if (la_.empty()) return true;
   PackJob* job = la_.front().get();
   const int state = job->state.load();
@@ -442,7 +513,10 @@ std::unique_ptr<PackJob> ChunkFeed::NextPackJob() {
     if (idle) {
       stats_->wait_pack_idle_sec += GetTime() - t0;
       // the link stood still for the pool: the pool cannot feed it alone
-      if (!cfg_.pack_wait) SetPoolBehind(true);
+      // (not so at a pass's start, for a piece queued ahead of the rewind)
+      if (WaitMeansPoolBehind(idle, cfg_.pack_wait, job->head && job->seq == 0)) {
+        SetPoolBehind(true);
+      }
     }
   }
   stats_->pack_sec = pool_->pack_sec();
@@ -478,6 +552,7 @@ void ChunkFeed::DropLookahead() {
   la_.clear();
   la_end_ = false;
   front_unpushed_ = false;
+  head_ = false;
   la_seq_ = submitted_ = la_pushed_ = 0;
   pool_->SetSubmitted(0);
 }
@@ -498,13 +573,13 @@ void ChunkFeed::StartCaching() {
     arena_bytes_ =
         PartitionBytes() + std::max(split_->files().size(), order_.all_segments().size()) + 16;
     arena_.reset(new DeviceBuffer(arena_bytes_ + kTextPadBytes));
-    DMLC_HIP_CHECK(hipMemsetAsync(arena_->get(), 0, arena_bytes_ + kTextPadBytes, copy_->get()));
+    MemsetOrdered(arena_->get(), arena_bytes_ + kTextPadBytes);
   }
   caching_ = true;
 }
 
-void ChunkFeed::DrainInflight() {
-  copy_->Synchronize();
+void ChunkFeed::DrainInflight(bool keep_head) {
+  SyncCopyStreams();
   if (unpack_) unpack_->Synchronize();
   DMLC_HIP_CHECK(hipStreamSynchronize(compute_));
   while (!inflight_.empty()) {
@@ -513,8 +588,13 @@ void ChunkFeed::DrainInflight() {
     inflight_.pop_front();
   }
   ReleasePackSlot(&cur_.pack_slot);
-  DropLookahead();
-  last_copy_d_ = -1;
+  if (keep_head) {
+    head_ = false;  // la_ is the new pass's lookahead from here on
+  } else {
+    DropLookahead();
+  }
+  last_copy_d_[0] = last_copy_d_[1] = -1;
+  pass_chunks_ = 0;
   reader_done_ = false;
   busy_ = 0;
 }
@@ -548,6 +628,7 @@ void ChunkFeed::Release(bool delivered) {
     if (cur_.d >= 0) (void)hipEventRecord(parsed_[cur_.d]->get(), compute_);
     busy_ = 0;
     ReleasePackSlot(&cur_.pack_slot);
+    if (head_) DropLookahead();  // a failed pass is not followed by its twin
     if (cur_.slot != nullptr) {
       try {
         iter_.Recycle(&cur_.slot);

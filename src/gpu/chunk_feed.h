@@ -4,11 +4,20 @@
  *  chunk by chunk, into HBM and hands each chunk to the parse on the compute
  *  stream.  No parsing here and nothing that depends on the index type.
  *
- * Per chunk, in stream order (d: its device slot):
- *   copy stream    : wait(parsed[d]) -> H2D(text[d]) -> record(copied[d])
- *   compute stream : wait(copied[d]) -> parse -> record(parsed[d])
+ * Per chunk, in stream order (d: its device slot, n: its number in the pass):
+ *   copy stream n&1 : wait(parsed[d]) -> H2D(text[d]) -> record(copied[d])
+ *   compute stream  : wait(copied[d]) -> parse -> record(parsed[d])
  * The H2D of the next chunks is queued before the current chunk is parsed, so
- * PCIe transfers overlap the kernels.
+ * PCIe transfers overlap the kernels.  Consecutive chunks alternate over two
+ * copy streams (cfg.copy_streams), so chunk n + 1's copy is dispatched while
+ * chunk n's runs and the link does not idle for the hand-over between two
+ * dependent copies of one stream.  Nothing is ordered by the copy streams'
+ * own order: a slot's copy, unpack and parse are chained by the slot's events
+ * alone, and a memset of slot or arena memory (construction, a regrown slot,
+ * StartCaching) is followed by an event both copy streams wait for
+ * (MemsetOrdered).  Drains synchronise both.  With cfg.hbm_cache there is one
+ * copy stream: only the first pass crosses the link, and a fifth stream in the
+ * process slowed the replay passes (profiles/link_idle/README.md).
  *
  * Three host sources feed the ring of device slots through one function
  * (NextPiece): the pinned ring (a reader thread fills pinned slots ahead,
@@ -22,18 +31,36 @@
  * 4-bit codes into the device slot's staging buffer and is expanded into the
  * slot's text (or its HBM-cache arena range) on a stream of its own, right
  * after its copied event; its parse waits for that:
- *   copy stream    : wait(parsed[d]) -> H2D(stage[d]) -> record(copied[d])
- *   unpack stream  : wait(copied[d]) -> unpack -> record(unpacked[d])
- *   compute stream : wait(unpacked[d]) -> parse -> record(parsed[d])
+ *   copy stream n&1 : wait(parsed[d]) -> H2D(stage[d]) -> record(copied[d])
+ *   unpack stream   : wait(copied[d]) -> unpack -> record(unpacked[d])
+ *   compute stream  : wait(unpacked[d]) -> parse -> record(parsed[d])
+ * stage[d] may be overwritten once parsed[d] is reached, on either copy
+ * stream: the parse that recorded it waited for unpacked[d], the last reader
+ * of stage[d].
  * A piece whose pack is not finished goes raw only when the link would
- * otherwise idle (pack_pool.h, DecideSubmit), on the same copy stream:
- *   copy stream    : wait(parsed[d]) -> H2D(text[d]) -> record(copied[d])
- * The first piece of a pass does.  While copied[] of the last submitted chunk
+ * otherwise idle (pack_pool.h, DecideSubmit), as any other chunk of the pass:
+ *   copy stream n&1 : wait(parsed[d]) -> H2D(text[d]) -> record(copied[d])
+ * The first piece of a pass does, unless it was packed ahead (below).  While
+ * copied[] of the last chunk submitted on either copy stream
  * is still outstanding, the piece is left to the pool and FillPipeline returns
  * with a device slot unfilled; Acquire, FirstSyncDone and the next Acquire try
  * again.  If the link ever has to wait for a pack, the pool is slower than the
  * link: until it has caught up, unstarted pieces next to the cursor go raw at
  * once.  The parse kernels see the same bytes either way.
+ *
+ * Head jobs (cfg.pack_head): the pool runs ahead of the link and idles before
+ * a pass ends, and a pass that starts cold sends its first piece raw.  So once
+ * the source has handed in the last piece of a pass, the first kHeadJobs
+ * pieces of the same order are fetched again and queued to the pool, with
+ * sequence numbers from 0.  Seek(0) / BeforeFirst adopts them as the new pass's
+ * lookahead (their pack slots, the source cursor after them); any other Seek,
+ * SetEpoch, a failed chunk or destruction quiesces the pool and drops them as
+ * any lookahead.  Only when the mapping outlives the rewind (the source is not
+ * windowed), the pass is unshuffled, the next pass is no HBM replay, pack_wait
+ * is off and the parser has been rewound to 0 after a completed pass before (a
+ * single pass pays nothing).  This is no cache: every pass packs, transfers and
+ * parses every byte; the head is only read from the mapping at the end of the
+ * previous pass instead of at the start of its own.
  *
  * HBM epoch cache (cfg.hbm_cache): the first full pass lands every chunk in
  * one device arena; later epochs replay it from there in the epoch's order
@@ -186,7 +213,14 @@ class ChunkFeed {
   static constexpr size_t kPackLookahead = 4;
   static constexpr size_t kPackDistance = 2;
   static constexpr size_t kPackCaughtUp = 8;
+  /*! \brief pieces of the next pass queued to the pool when a pass ends: the
+   *  second is packed while the first crosses the link */
+  static constexpr size_t kHeadJobs = 2;
 
+  void SyncCopyStreams() const;
+  void MemsetOrdered(void* ptr, size_t bytes);
+  void FetchLookahead(size_t limit, bool head);
+  void QueueHeadJobs();
   void StartReader();
   void StartPacking(bool csv_alphabet);
   void StartCaching();
@@ -202,7 +236,7 @@ class ChunkFeed {
   void RescueLookahead();
   void DropLookahead();
   void ReleasePackSlot(int* pack_slot);
-  void DrainInflight();
+  void DrainInflight(bool keep_head = false);
 
   DeviceParserConfig cfg_;
   hipStream_t compute_;
@@ -210,7 +244,14 @@ class ChunkFeed {
   std::unique_ptr<io::InputSplitBase> split_;
   std::unique_ptr<io::ShardReader> reader_;
   EpochOrder order_;
-  std::unique_ptr<Stream> copy_;
+  /*! \brief chunk n of a pass is copied on stream n % ncopy_ */
+  std::unique_ptr<Stream> copy_[2];
+  size_t ncopy_{2};
+  /*! \brief chunks submitted in this pass */
+  size_t pass_chunks_{0};
+  /*! \brief recorded after a memset of slot or arena memory; both copy
+   *  streams wait for it */
+  std::unique_ptr<Event> zeroed_;
   std::vector<std::unique_ptr<DeviceBuffer>> dtext_;
   std::vector<std::unique_ptr<Event>> copied_, parsed_;
   ThreadedIter<HostSlot> iter_;
@@ -231,8 +272,15 @@ class ChunkFeed {
   size_t packed_in_a_row_{0};
   /*! \brief PreparePackJob's decision for the front piece */
   SubmitAction next_action_{SubmitAction::kSubmit};
-  /*! \brief device slot of the last chunk submitted in this pass (-1: none) */
-  int last_copy_d_{-1};
+  /*! \brief la_ holds head jobs: pieces of the next pass, queued when this
+   *  one's last piece was handed in */
+  bool head_{false};
+  /*! \brief this parser was rewound to 0 after a completed pass: its user runs
+   *  pass after pass, and head jobs are worth queueing */
+  bool head_armed_{false};
+  /*! \brief per copy stream, the device slot of the last chunk submitted on it
+   *  in this pass (-1: none) */
+  int last_copy_d_[2]{-1, -1};
   std::vector<PinnedBuffer> pack_slots_;
   std::vector<int> free_pack_slots_;
   std::vector<std::unique_ptr<DeviceBuffer>> dstage_;

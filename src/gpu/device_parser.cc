@@ -97,6 +97,10 @@ void DeviceParserConfig::Update(const std::map<std::string, std::string>& args) 
       zero_copy = (v == "auto" || v == "-1") ? -1 : ((v == "0" || v == "false") ? 0 : 1);
     } else if (k == "pack_wait") {
       pack_wait = v != "0" && v != "false";
+    } else if (k == "pack_head") {
+      pack_head = v != "0" && v != "false";
+    } else if (k == "copy_streams") {
+      copy_streams = std::atoi(v.c_str());
     } else if (k == "packed_h2d") {
       packed_h2d = (v == "auto" || v == "-1") ? -1 : ((v == "0" || v == "false") ? 0 : 1);
     }
@@ -109,6 +113,7 @@ void DeviceParserConfig::Update(const std::map<std::string, std::string>& args) 
   CHECK_LT(replay_chunk_bytes, size_t(1) << 31) << "replay_chunk_bytes must be < 2 GiB";
   CHECK_GE(pinned_slots, 1);
   CHECK_GE(device_slots, 1);
+  CHECK(copy_streams == 1 || copy_streams == 2) << "copy_streams must be 1 or 2";
   CHECK_GE(shuffle_parts, 1U) << "shuffle_parts must be >= 1";
 }
 

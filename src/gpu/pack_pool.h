@@ -66,6 +66,9 @@ struct PackJob {
   uint32_t nexc{0};
   /*! \brief the piece's bytes were copied into the slot (its window goes away) */
   bool rescued{false};
+  /*! \brief queued at the end of the previous pass for the start of this one
+   *  (a head job: chunk_feed.h) */
+  bool head{false};
 };
 
 /*! \brief what the submit loop does with the piece at its cursor */
@@ -104,6 +107,18 @@ inline SubmitAction DecideSubmit(int state, bool pack_wait, bool nothing_infligh
   if (pack_wait) return SubmitAction::kWait;
   if (!nothing_inflight && !pool_behind && link_busy()) return SubmitAction::kDefer;
   return state == PackJob::kQueued ? SubmitAction::kClaimRaw : SubmitAction::kWait;
+}
+
+/*!
+ * \brief whether a wait for a pack (SubmitAction::kWait) shows that the pool is
+ *  slower than the link.  It does when the wait began with no copy outstanding,
+ *  unless every pack is waited for anyway (pack_wait), and unless the piece is
+ *  the first of a pass that was queued ahead of the rewind (a head job): the
+ *  link is idle there because the pass has only begun, not because the pool
+ *  fell behind it.
+ */
+inline bool WaitMeansPoolBehind(bool link_idle, bool pack_wait, bool head_of_pass) {
+  return link_idle && !pack_wait && !head_of_pass;
 }
 
 class PackPool {

@@ -478,6 +478,7 @@ class PyDeviceParser {
     d["raw_chunks"] = s.raw_chunks;
     d["link_bytes"] = s.link_bytes;
     d["exception_blocks"] = s.exception_blocks;
+    d["head_packed"] = s.head_packed;
     d["pack_sec"] = s.pack_sec;
     d["wait_pack_sec"] = s.wait_pack_sec;
     d["wait_pack_idle_sec"] = s.wait_pack_idle_sec;
