@@ -11,9 +11,9 @@ from typing import Optional
 
 import torch
 
-from ..ops import csr_spmm, csr_spmv, hashed_dense
+from ..ops import csr_ffm, csr_spmm, csr_spmv, hashed_dense
 
-__all__ = ["SparseLogReg", "HashedFM", "SparseSoftmaxReg", "SparseFM"]
+__all__ = ["SparseLogReg", "HashedFM", "SparseSoftmaxReg", "SparseFM", "SparseFFM"]
 
 
 class SparseLogReg(torch.nn.Module):
@@ -153,6 +153,85 @@ class SparseFM(torch.nn.Module):
         """fp32 reference of the same model on a dense batch
         (:meth:`HashedFM.reference`)."""
         return HashedFM.reference(x, w, v, bias)
+
+
+class SparseFFM(torch.nn.Module):
+    """Field-aware factorisation machine on a LibFM batch (``field:index:value``
+    entries): over a row's entries a with id ``i_a``, field ``f_a``, value ``x_a``
+
+        y = b + sum_a x_a w[i_a] + sum_{a < b} x_a x_b <v[i_a, f_b, :], v[i_b, f_a, :]>
+
+    with ``w`` [F, 1] and ``v`` [F, num_fields, rank] (``randn * 0.01`` from
+    ``seed``, as :class:`SparseFM`).  Pairs run over entries: repeated ids in a
+    row are separate entries.  On the device the pairwise term is
+    :func:`~dmlc_core_amd.ops.csr_ffm` (rank a multiple of 4 up to 32; an id
+    >= F or a field >= num_fields raises ``ValueError``) and the linear term
+    :func:`~dmlc_core_amd.ops.csr_spmv` with its cached-transpose gradient; on
+    host tensors :meth:`reference` evaluates the definition with torch ops."""
+
+    def __init__(self, num_features: int, num_fields: int, rank: int = 4, seed: int = 0):
+        super().__init__()
+        self.num_features, self.num_fields = int(num_features), int(num_fields)
+        self.rank, self.seed = int(rank), int(seed)
+        g = torch.Generator(device="cpu")
+        g.manual_seed(self.seed)
+        self.bias = torch.nn.Parameter(torch.zeros(1))
+        self.w = torch.nn.Parameter(torch.zeros(self.num_features, 1))
+        self.v = torch.nn.Parameter(
+            torch.randn(self.num_features, self.num_fields, self.rank, generator=g) * 0.01)
+
+    def forward(self, csr) -> torch.Tensor:
+        if not csr["index"].is_cuda:
+            return self.reference(csr, self.w, self.v, self.bias)
+        return csr_spmv(csr, self.w.reshape(-1), self.bias) + csr_ffm(csr, self.v)
+
+    def loss(self, csr, loss: str = "logistic") -> torch.Tensor:
+        """Mean ``"logistic"`` (labels in [0, 1]) or ``"squared"`` loss against
+        ``csr["label"]``, row-weighted by ``csr["weight"]`` if present
+        (``mean(weight * loss)``), as :meth:`SparseFM.loss`."""
+        if loss not in _FM_LOSSES:
+            raise ValueError(f"loss must be one of {sorted(_FM_LOSSES)}, got {loss!r}")
+        y = self.forward(csr)
+        lab, weight = csr["label"].to(y.dtype), csr.get("weight")
+        if loss == "logistic":
+            return torch.nn.functional.binary_cross_entropy_with_logits(y, lab, weight=weight)
+        err = (y - lab) ** 2
+        return (err * weight).mean() if weight is not None else err.mean()
+
+    @staticmethod
+    def reference(csr, w, v, bias) -> torch.Tensor:
+        """The model's definition on host tensors, in the dtype of ``w`` / ``v``
+        (differentiable): every pair a < b of every row is listed and summed
+        with ``index_add``.  A densified batch cannot stand in here, because
+        the field belongs to the entry, not to the feature."""
+        def signed(t):  # the parser's unsigned arrays, as torch computes with them
+            if t.dtype in (torch.uint32, torch.uint64):
+                t = t.view(torch.int32 if t.dtype == torch.uint32 else torch.int64)
+            return t.to(torch.int64)
+
+        off = signed(csr["offset"])
+        rows = off.numel() - 1
+        lo = int(off[0])
+        lens = off[1:] - off[:-1]
+        nnz = int(lens.sum())
+        idx = signed(csr["index"])[lo:lo + nnz]
+        fld = signed(csr["field"])[lo:lo + nnz]
+        x = torch.ones(nnz, dtype=w.dtype) if csr.get("value") is None \
+            else csr["value"][lo:lo + nnz].to(w.dtype)
+        row = torch.repeat_interleave(torch.arange(rows), lens)
+        y = bias + torch.zeros(rows, dtype=w.dtype).index_add(0, row, x * w[idx, 0])
+        first, second, owner = [], [], []
+        for r, (b, n) in enumerate(zip((off[:-1] - lo).tolist(), lens.tolist())):
+            if n >= 2:
+                a, c = torch.triu_indices(n, n, 1)
+                first.append(a + b)
+                second.append(c + b)
+                owner.append(torch.full((a.numel(),), r, dtype=torch.int64))
+        if first:
+            a, c, owner = torch.cat(first), torch.cat(second), torch.cat(owner)
+            term = x[a] * x[c] * (v[idx[a], fld[c]] * v[idx[c], fld[a]]).sum(-1)
+            y = y + torch.zeros(rows, dtype=w.dtype).index_add(0, owner, term)
+        return y
 
 
 class _HashedFMFunction(torch.autograd.Function):

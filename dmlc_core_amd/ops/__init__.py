@@ -2,7 +2,7 @@
 
 Every op launches a hand-written CDNA4 kernel from ``libdmlc.so`` on the
 current torch stream (src/gpu/feature_kernels.hip, spmm_kernels.hip,
-transpose_kernels.hip, gather_kernels.hip).  There is no PyTorch
+transpose_kernels.hip, gather_kernels.hip, ffm_kernels.hip).  There is no PyTorch
 fallback: on a machine without the extension or a GPU these functions raise.
 
 CSR arguments are the dict returned by :func:`dmlc_core_amd.data.csr_to_torch`
@@ -19,7 +19,8 @@ from .. import _dmlc
 
 __all__ = ["spmv", "spmv_t", "hashed_dense", "SpMVFunction", "csr_spmv", "transpose",
            "gather_rows", "gather_buffers", "release_workspace",
-           "spmm", "spmm_t", "SpMMFunction", "csr_spmm"]
+           "spmm", "spmm_t", "SpMMFunction", "csr_spmm",
+           "ffm", "ffm_t", "FFMFunction", "csr_ffm"]
 
 # persistent transpose scratch per (device, stream), grow-only: a rebuild (a
 # further shard, a refreshed batch) allocates no multi-GB scratch again
@@ -196,6 +197,121 @@ def spmm_t(csr: Dict, d: torch.Tensor, num_features: int) -> torch.Tensor:
     _dmlc.spmm_t(_ptr(csr["offset"]), _ptr(csr["index"]), _ptr(csr.get("value")), nrows, _ptr(d), k,
                  _ptr(g), _stream(), _index64(csr))
     return g
+
+
+_FFM_ERR_INDEX, _FFM_ERR_FIELD = 1, 2  # kFFMErr* (src/gpu/kernels.h)
+
+
+def _check_factors(v) -> int:
+    """the factor table of :func:`ffm` / :func:`ffm_t`, before anything is
+    launched; returns its rank k"""
+    if not isinstance(v, torch.Tensor) or v.dim() != 3:
+        raise ValueError("v must be a 3-D tensor [F, num_fields, k]")
+    if v.dtype != torch.float32:
+        raise ValueError(f"v must be float32, got {v.dtype}")
+    k, kmax = int(v.shape[2]), int(_dmlc.ffm_max_rank())
+    if k % 4 != 0 or not 4 <= k <= kmax:
+        raise ValueError(f"v must have a rank k that is a multiple of 4 from 4 to {kmax}, got {k}")
+    if v.shape[1] < 1:
+        raise ValueError("v must have at least one field")
+    if not v.is_contiguous():
+        raise ValueError("v must be contiguous (row-major)")
+    if v.data_ptr() % 16:
+        raise ValueError("v must be 16-byte aligned (the kernels' 16-byte loads)")
+    return k
+
+
+def _check_fields(name: str, csr: Dict) -> Dict:
+    """``csr`` as :func:`ffm` / :func:`ffm_t` take it: a contiguous device CSR
+    with one ``field`` per entry, of the index's dtype"""
+    if _paired(csr):
+        raise ValueError(f"{name}: a transpose's pair views carry no fields "
+                         "(a transpose has no field per entry)")
+    field, index = csr.get("field"), csr["index"]
+    if not isinstance(field, torch.Tensor):
+        raise ValueError(f"{name}: csr has no 'field' tensor (parse with format=\"libfm\")")
+    if field.dtype != index.dtype:
+        raise ValueError(f"csr['field'] must have index's dtype ({index.dtype}), got {field.dtype}")
+    _check(csr)
+    if not field.is_cuda or not field.is_contiguous() or field.device != index.device:
+        raise ValueError("csr['field'] must be a contiguous device tensor")
+    if field.numel() != index.numel():
+        raise ValueError(f"csr['field'] has {field.numel()} entries, csr['index'] {index.numel()}")
+    if csr.get("value") is not None and csr["value"].numel() != index.numel():
+        raise ValueError(f"csr['value'] has {csr['value'].numel()} entries, "
+                         f"csr['index'] {index.numel()}")
+    return csr
+
+
+def ffm(csr: Dict, v: torch.Tensor, validate: bool = True) -> torch.Tensor:
+    """The pairwise term of a field-aware factorisation machine (FF1,
+    src/gpu/ffm_kernels.hip), float32 ``[rows]``: over a row's entries a with
+    id ``i_a``, field ``f_a`` and value ``x_a`` (1.0 without ``value``)
+
+        p[r] = sum_{a < b} x_a x_b sum_c v[i_a, f_b, c] * v[i_b, f_a, c]
+
+    Pairs run over entries, not distinct ids: two entries with the same id (or
+    the same id and field) form a pair like any other; rows of 0 or 1 entries
+    give 0.  ``csr``: a LibFM CSR (``csr_to_torch`` / ``gather_rows`` / a row
+    slice) with a contiguous device ``field`` of index's dtype, one per entry;
+    a transpose's pair views are rejected (a transpose has no fields).  ``v``:
+    a contiguous float32 device tensor ``[F, num_fields, k]``, k a multiple of
+    4 from 4 to ``_dmlc.ffm_max_rank()`` (32).  Anything else raises
+    ``ValueError`` before a launch.
+
+    An entry whose id is ``>= F`` or whose field is ``>= num_fields`` is
+    skipped on the device (it takes part in no pair and no address is formed
+    from it) and flagged: ``validate=True`` reads the flag word -- the one
+    device-to-host read of the call -- and raises ``ValueError`` naming which
+    of the two was out of range; ``validate=False`` reads nothing and returns
+    the sums over the remaining entries.  Rows of up to
+    ``_dmlc.ffm_staged_row_entries()`` entries are staged in LDS once, longer
+    rows re-read global memory.  No atomics, a summation order fixed by the
+    row's length and k: the same inputs give the same bytes."""
+    k = _check_factors(v)
+    csr = _check_fields("ffm", csr)
+    _check_device("v", v, csr)
+    nrows = csr["offset"].numel() - 1
+    y = torch.empty(nrows, dtype=torch.float32, device=v.device)
+    err = torch.zeros(1, dtype=torch.int32, device=v.device)
+    _dmlc.ffm_forward(_ptr(csr["offset"]), _ptr(csr["index"]), _ptr(csr.get("value")),
+                      _ptr(csr["field"]), nrows, _ptr(v), int(v.shape[0]), int(v.shape[1]), k,
+                      _ptr(y), _ptr(err), _stream(), _index64(csr))
+    if validate:
+        bits = int(err.item())
+        if bits:
+            what = [s for b, s in ((_FFM_ERR_INDEX, f"a feature id is >= F ({v.shape[0]})"),
+                                   (_FFM_ERR_FIELD, f"a field is >= num_fields ({v.shape[1]})"))
+                    if bits & b]
+            raise ValueError("ffm: " + " and ".join(what))
+    return y
+
+
+def ffm_t(csr: Dict, g: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+    """The gradient of :func:`ffm` in ``v`` for an upstream ``g`` (FF2, no-return
+    f32 atomics into a zeroed ``[F, num_fields, k]`` result): for every ordered
+    pair a != b of every row ``dV[i_a, f_b, :] += g[r] x_a x_b v[i_b, f_a, :]``.
+    ``g``: a contiguous float32 device tensor ``[rows]``; ``csr`` and ``v`` as
+    for :func:`ffm`.  Rows whose ``g`` is +-0 are skipped, out-of-range entries
+    are skipped as in :func:`ffm` (nothing is read back here), and a CSR of no
+    rows gives zeros.  The sums are in no fixed order: a deterministic,
+    atomic-free gradient (a gather over the transpose that walks each row
+    again) is not provided."""
+    k = _check_factors(v)
+    if not isinstance(g, torch.Tensor) or g.dim() != 1 or g.dtype != torch.float32 \
+            or not g.is_contiguous():
+        raise ValueError("g must be a contiguous float32 tensor [rows]")
+    csr = _check_fields("ffm_t", csr)
+    _check_device("v", v, csr)
+    _check_device("g", g, csr)
+    nrows = csr["offset"].numel() - 1
+    if g.numel() != nrows:
+        raise ValueError(f"g has {g.numel()} entries, the CSR {nrows} rows")
+    dv = torch.zeros_like(v)
+    _dmlc.ffm_backward(_ptr(csr["offset"]), _ptr(csr["index"]), _ptr(csr.get("value")),
+                       _ptr(csr["field"]), nrows, _ptr(g), _ptr(v), int(v.shape[0]),
+                       int(v.shape[1]), k, _ptr(dv), _stream(), _index64(csr))
+    return dv
 
 
 def hashed_dense(csr: Dict, dim: int, seed: int = 0, fp8: bool = True,
@@ -575,6 +691,35 @@ class SpMMFunction(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             gb = grad_out.sum(0)
         return gw, gb, None, None, None
+
+
+class FFMFunction(torch.autograd.Function):
+    """Autograd wrapper: forward = ffm(csr, v), backward d/dv = ffm_t(csr, g, v)
+    (FF2, f32 atomics).  The id / field check runs in forward only."""
+
+    @staticmethod
+    def forward(ctx, v, csr_tuple, validate):
+        offset, index, value, field = csr_tuple
+        ctx.csr = {"offset": offset, "index": index, "value": value, "field": field}
+        ctx.save_for_backward(v)
+        return ffm(ctx.csr, v.detach(), validate)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (v,) = ctx.saved_tensors
+        gv = None
+        if ctx.needs_input_grad[0]:
+            gv = ffm_t(ctx.csr, grad_out.contiguous().float(), v.detach())
+        return gv, None, None
+
+
+def csr_ffm(csr: Dict, v: torch.Tensor, validate: bool = True) -> torch.Tensor:
+    """Differentiable :func:`ffm` (its arguments and checks), differentiable in
+    ``v``: the backward is :func:`ffm_t`, whose atomic sums are in no fixed
+    order.  ``validate`` applies to the forward; the backward reads nothing
+    back."""
+    return FFMFunction.apply(v, (csr["offset"], csr["index"], csr.get("value"), csr.get("field")),
+                             validate)
 
 
 def csr_spmv(csr: Dict, w: torch.Tensor, bias: torch.Tensor, grad: str = "auto") -> torch.Tensor:

@@ -17,6 +17,8 @@
  *   M1 spmm              LaunchCSRSpMM            (spmm_kernels.hip)
  *   M1p spmm over pairs  LaunchCSRSpMMPairs       (spmm_kernels.hip)
  *   M2 spmm transposed   LaunchCSRSpMMT           (spmm_kernels.hip)
+ *   FF1 ffm forward      LaunchFFMForward         (ffm_kernels.hip)
+ *   FF2 ffm backward     LaunchFFMBackward        (ffm_kernels.hip)
  *   G1 row gather count  LaunchCSRGatherCount     (gather_kernels.hip)
  *   G2 row gather fill   LaunchCSRGatherFill      (gather_kernels.hip)
  * All launchers are asynchronous on `stream` and never allocate or
@@ -433,6 +435,40 @@ void LaunchCSRSpMMPairs(const uint64_t* offset, const void* pairs, size_t nrows,
 template <typename IndexType>
 void LaunchCSRSpMMT(const uint64_t* offset, const IndexType* index, const float* value,
                     size_t nrows, const float* d, int k, float* g, hipStream_t stream);
+// -------------------- field-aware FM (ffm_kernels.hip) ---------------------
+/*! \brief largest factor rank k of FF1 / FF2 (k: a multiple of 4 from 4) */
+constexpr int kFFMMaxRank = 32;
+/*! \brief entries of a row FF1 / FF2 stage in LDS; longer rows re-read global memory */
+constexpr uint32_t kFFMStagedRowEntries = 128;
+/*! \brief bits FF1 ORs into its error word: an id >= features, a field >= num_fields */
+constexpr uint32_t kFFMErrIndex = 1, kFFMErrField = 2;
+/*!
+ * \brief FF1: y[r] = sum_{a < b} x_a x_b sum_c v[i_a, f_b, c] v[i_b, f_a, c] over
+ *  the entries (i, f, x) of row r, for a row-major contiguous, 16-byte aligned
+ *  f32 v [features x num_fields x k].  Pairs run over entries, not distinct
+ *  ids; rows of 0 or 1 entries give 0.  The CSR shapes of K11 (value may be
+ *  nullptr, offset a slice of a larger row pointer, no rows) with a field per
+ *  entry, of the index's type.  An entry with id >= features or field >=
+ *  num_fields takes part in no pair, is never turned into an address, and ORs
+ *  kFFMErrIndex / kFFMErrField into *error (an int32 the caller zeroed).  No
+ *  atomics on y; the summation order depends on the row's length and k alone.
+ */
+template <typename IndexType>
+void LaunchFFMForward(const uint64_t* offset, const IndexType* index, const float* value,
+                      const IndexType* field, size_t nrows, const float* v, uint64_t features,
+                      int num_fields, int k, float* y, int* error, hipStream_t stream);
+/*!
+ * \brief FF2: dv[i_a, f_b, :] += g[r] x_a x_b v[i_b, f_a, :] for every ordered
+ *  pair a != b of every row, with no-return f32 atomics into a zeroed dv shaped
+ *  as v.  One wave per row, a fixed per wave-instruction, the lanes over (b, c)
+ *  with c fastest: for entries in field order one instruction's targets are one
+ *  contiguous stretch of dv[i_a, :, :].  Rows with g[r] == +-0 are skipped;
+ *  out-of-range entries are skipped as in FF1 (nothing is reported here).
+ */
+template <typename IndexType>
+void LaunchFFMBackward(const uint64_t* offset, const IndexType* index, const float* value,
+                       const IndexType* field, size_t nrows, const float* g, const float* v,
+                       uint64_t features, int num_fields, int k, float* dv, hipStream_t stream);
 // ------------------------ HashedFM (fm_kernels.hip) ------------------------
 /*! \brief factor rank of the HIP HashedFM kernels and the [w | V] column count */
 constexpr int kFmRank = 16;

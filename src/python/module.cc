@@ -990,6 +990,58 @@ PYBIND11_MODULE(_dmlc, m) {
   m.def("spmm_max_cols", []() { return gpu::kSpMMMaxCols; },
         "widest dense operand (columns) ops.spmm / ops.spmm_t take");
   m.def(
+      "ffm_forward",
+      [stream_of](uintptr_t offset, uintptr_t index, uintptr_t value, uintptr_t field, size_t nrows,
+                  uintptr_t v, uint64_t features, int num_fields, int k, uintptr_t y,
+                  uintptr_t error, uintptr_t stream, bool index64) {
+        auto* off = reinterpret_cast<const uint64_t*>(offset);
+        auto* val = reinterpret_cast<const float*>(value);
+        if (index64) {
+          gpu::LaunchFFMForward<uint64_t>(off, reinterpret_cast<const uint64_t*>(index), val,
+                                          reinterpret_cast<const uint64_t*>(field), nrows,
+                                          reinterpret_cast<const float*>(v), features, num_fields, k,
+                                          reinterpret_cast<float*>(y),
+                                          reinterpret_cast<int*>(error), stream_of(stream));
+        } else {
+          gpu::LaunchFFMForward<uint32_t>(off, reinterpret_cast<const uint32_t*>(index), val,
+                                          reinterpret_cast<const uint32_t*>(field), nrows,
+                                          reinterpret_cast<const float*>(v), features, num_fields, k,
+                                          reinterpret_cast<float*>(y),
+                                          reinterpret_cast<int*>(error), stream_of(stream));
+        }
+      },
+      py::arg("offset"), py::arg("index"), py::arg("value"), py::arg("field"), py::arg("nrows"),
+      py::arg("v"), py::arg("features"), py::arg("num_fields"), py::arg("k"), py::arg("y"),
+      py::arg("error"), py::arg("stream"), py::arg("index64") = false);
+  m.def(
+      "ffm_backward",
+      [stream_of](uintptr_t offset, uintptr_t index, uintptr_t value, uintptr_t field, size_t nrows,
+                  uintptr_t g, uintptr_t v, uint64_t features, int num_fields, int k, uintptr_t dv,
+                  uintptr_t stream, bool index64) {
+        auto* off = reinterpret_cast<const uint64_t*>(offset);
+        auto* val = reinterpret_cast<const float*>(value);
+        if (index64) {
+          gpu::LaunchFFMBackward<uint64_t>(off, reinterpret_cast<const uint64_t*>(index), val,
+                                           reinterpret_cast<const uint64_t*>(field), nrows,
+                                           reinterpret_cast<const float*>(g),
+                                           reinterpret_cast<const float*>(v), features, num_fields,
+                                           k, reinterpret_cast<float*>(dv), stream_of(stream));
+        } else {
+          gpu::LaunchFFMBackward<uint32_t>(off, reinterpret_cast<const uint32_t*>(index), val,
+                                           reinterpret_cast<const uint32_t*>(field), nrows,
+                                           reinterpret_cast<const float*>(g),
+                                           reinterpret_cast<const float*>(v), features, num_fields,
+                                           k, reinterpret_cast<float*>(dv), stream_of(stream));
+        }
+      },
+      py::arg("offset"), py::arg("index"), py::arg("value"), py::arg("field"), py::arg("nrows"),
+      py::arg("g"), py::arg("v"), py::arg("features"), py::arg("num_fields"), py::arg("k"),
+      py::arg("dv"), py::arg("stream"), py::arg("index64") = false);
+  m.def("ffm_max_rank", []() { return gpu::kFFMMaxRank; },
+        "largest factor rank (a multiple of 4) ops.ffm / ops.ffm_t take");
+  m.def("ffm_staged_row_entries", []() { return gpu::kFFMStagedRowEntries; },
+        "entries of a row FF1 / FF2 stage in LDS; longer rows re-read global memory");
+  m.def(
       "csr_transpose",
       [stream_of](uintptr_t offset, size_t nrows, uint64_t base, uint64_t nnz, uintptr_t index,
                   uintptr_t value, uint64_t num_features, uintptr_t col_ptr, uintptr_t row_out,
