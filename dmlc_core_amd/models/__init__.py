@@ -11,7 +11,7 @@ from typing import Optional
 
 import torch
 
-from ..ops import csr_ffm, csr_spmm, csr_spmv, hashed_dense
+from ..ops import _stream, csr_ffm, csr_spmm, csr_spmv, hashed_dense
 
 __all__ = ["SparseLogReg", "HashedFM", "SparseSoftmaxReg", "SparseFM", "SparseFFM"]
 
@@ -139,14 +139,9 @@ class SparseFM(torch.nn.Module):
         """Mean ``"logistic"`` (labels in [0, 1]) or ``"squared"`` loss against
         ``csr["label"]``, row-weighted by ``csr["weight"]`` if present
         (``mean(weight * loss)``), as :meth:`HashedFM.loss`."""
-        if loss not in _FM_LOSSES:
-            raise ValueError(f"loss must be one of {sorted(_FM_LOSSES)}, got {loss!r}")
+        _check_loss(loss)
         y = self.forward(csr)
-        lab, weight = csr["label"].to(y.dtype), csr.get("weight")
-        if loss == "logistic":
-            return torch.nn.functional.binary_cross_entropy_with_logits(y, lab, weight=weight)
-        err = (y - lab) ** 2
-        return (err * weight).mean() if weight is not None else err.mean()
+        return _fm_loss(y, csr["label"], csr.get("weight"), loss)
 
     @staticmethod
     def reference(x: torch.Tensor, w, v, bias) -> torch.Tensor:
@@ -189,14 +184,9 @@ class SparseFFM(torch.nn.Module):
         """Mean ``"logistic"`` (labels in [0, 1]) or ``"squared"`` loss against
         ``csr["label"]``, row-weighted by ``csr["weight"]`` if present
         (``mean(weight * loss)``), as :meth:`SparseFM.loss`."""
-        if loss not in _FM_LOSSES:
-            raise ValueError(f"loss must be one of {sorted(_FM_LOSSES)}, got {loss!r}")
+        _check_loss(loss)
         y = self.forward(csr)
-        lab, weight = csr["label"].to(y.dtype), csr.get("weight")
-        if loss == "logistic":
-            return torch.nn.functional.binary_cross_entropy_with_logits(y, lab, weight=weight)
-        err = (y - lab) ** 2
-        return (err * weight).mean() if weight is not None else err.mean()
+        return _fm_loss(y, csr["label"], csr.get("weight"), loss)
 
     @staticmethod
     def reference(csr, w, v, bias) -> torch.Tensor:
@@ -282,6 +272,22 @@ class _HashedFMFunction(torch.autograd.Function):
 _FM_LOSSES = {"logistic": 0, "squared": 1}
 
 
+def _check_loss(loss: str) -> None:
+    if loss not in _FM_LOSSES:
+        raise ValueError(f"loss must be one of {sorted(_FM_LOSSES)}, got {loss!r}")
+
+
+def _fm_loss(y: torch.Tensor, label: torch.Tensor, weight: Optional[torch.Tensor],
+             loss: str) -> torch.Tensor:
+    """mean ``loss`` (one of ``_FM_LOSSES``) of the logits ``y`` against
+    ``label``, row-weighted by ``weight`` if given (``mean(weight * loss)``)"""
+    lab = label.to(y.dtype)
+    if loss == "logistic":
+        return torch.nn.functional.binary_cross_entropy_with_logits(y, lab, weight=weight)
+    err = (y - lab) ** 2
+    return (err * weight).mean() if weight is not None else err.mean()
+
+
 class _HashedFMLossFunction(torch.autograd.Function):
     """Forward + loss + backward of one HashedFM step as one HIP kernel over
     the fp8 batch (F5 k_fm_fused, src/gpu/fm_kernels.hip), then F3/F4 for dw,
@@ -335,10 +341,6 @@ def _dmlc():
     return ext
 
 
-def _stream() -> int:
-    return int(torch.cuda.current_stream().cuda_stream)
-
-
 _CUS = {}
 
 
@@ -390,8 +392,7 @@ class HashedFM(torch.nn.Module):
         instead of twice); its backward only scales the gradients it already
         holds.  Elsewhere: ``forward`` then the torch loss.  The logits of the
         last call are kept in ``self.last_logits``."""
-        if loss not in _FM_LOSSES:
-            raise ValueError(f"loss must be one of {sorted(_FM_LOSSES)}, got {loss!r}")
+        _check_loss(loss)
         if self._native(x8) and self.dim in (128, 256, 512, 1024) and x8.shape[0] > 0:
             self.gemm = "hip_mfma_bf16_fused"
             y = torch.empty(x8.shape[0], dtype=torch.float32, device=x8.device)
@@ -401,11 +402,7 @@ class HashedFM(torch.nn.Module):
             return out
         y = self.forward(x8, scale)
         self.last_logits = y.detach()
-        lab = label.to(y.dtype)
-        if loss == "logistic":
-            return torch.nn.functional.binary_cross_entropy_with_logits(y, lab, weight=weight)
-        err = (y - lab) ** 2
-        return (err * weight).mean() if weight is not None else err.mean()
+        return _fm_loss(y, label, weight, loss)
 
     def forward(self, x8: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
         if self._native(x8):

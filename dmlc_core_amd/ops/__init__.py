@@ -47,10 +47,6 @@ def _ptr(t) -> int:
     return 0 if t is None else int(t.data_ptr())
 
 
-def _index64(csr: Dict) -> bool:
-    return csr["index"].element_size() == 8
-
-
 def _paired(csr: Dict) -> bool:
     """index / value are the interleaved (int32 index, float32 value) pair
     views :func:`transpose` returns: value's storage is index's shifted by one
@@ -92,6 +88,30 @@ def _stream() -> int:
     return int(torch.cuda.current_stream().cuda_stream)
 
 
+def _describe(csr: Dict, pairs: bool = False) -> tuple:
+    """``csr`` as every CSR op of ``_dmlc`` takes it (gpu::CsrView): the
+    addresses of offset, index, value and field (0: none), the rows, whether
+    the indices are 64-bit, and -- for an op that reads them (``pairs``) --
+    whether index / value are a transpose's interleaved pairs"""
+    field = csr.get("field")
+    return (_ptr(csr["offset"]), _ptr(csr["index"]), _ptr(csr.get("value")),
+            _ptr(field if isinstance(field, torch.Tensor) else None), csr["offset"].numel() - 1,
+            csr["index"].element_size() == 8, pairs and _paired(csr))
+
+
+def _view(csr: Dict, *, pairs: bool = False, fields=False):
+    """check ``csr`` (:func:`_check`; ``fields``: the name of an op that needs a
+    field per entry, :func:`_check_fields`) and return its :func:`_describe`
+    tuple and row count.  The tuple holds addresses: ``csr`` must outlive the
+    launch's enqueue, so the caller unpairs (:func:`_unpair`) and keeps the dict"""
+    if fields:
+        _check_fields(fields, csr)
+    else:
+        _check(csr, pairs)
+    view = _describe(csr, pairs)
+    return view, view[4]
+
+
 def spmv(csr: Dict, w: torch.Tensor, bias: float = 0.0) -> torch.Tensor:
     """y[r] = sum_j value[j] * w[index[j]] + bias  (K11, 16 lanes per row).
     Takes contiguous arrays or a transpose's interleaved (index, value) pairs.
@@ -100,12 +120,10 @@ def spmv(csr: Dict, w: torch.Tensor, bias: float = 0.0) -> torch.Tensor:
     ``offset`` may be a slice of a larger CSR's row pointer (``offset[0] !=
     0``) next to the whole ``index`` / ``value``.  Sums are f32, in no fixed
     order."""
-    _check(csr, pairs=True)
+    view, nrows = _view(csr, pairs=True)
     assert w.dtype == torch.float32 and w.is_cuda and w.is_contiguous()
-    nrows = csr["offset"].numel() - 1
     y = torch.empty(nrows, dtype=torch.float32, device=w.device)
-    _dmlc.spmv(_ptr(csr["offset"]), _ptr(csr["index"]), _ptr(csr.get("value")), nrows, _ptr(w),
-               float(bias), _ptr(y), _stream(), _index64(csr))
+    _dmlc.spmv(view, _ptr(w), float(bias), _ptr(y), _stream())
     return y
 
 
@@ -115,12 +133,10 @@ def spmv_t(csr: Dict, d: torch.Tensor, num_features: int) -> torch.Tensor:
     Takes the same CSR shapes as :func:`spmv`; rows whose ``d`` is +-0 are
     skipped (they add nothing), and a CSR of no rows gives zeros."""
     csr = _unpair(csr)
-    _check(csr)
+    view, _ = _view(csr)
     assert d.dtype == torch.float32 and d.is_cuda and d.is_contiguous()
     g = torch.zeros(num_features, dtype=torch.float32, device=d.device)
-    nrows = csr["offset"].numel() - 1
-    _dmlc.spmv_t(_ptr(csr["offset"]), _ptr(csr["index"]), _ptr(csr.get("value")), nrows, _ptr(d),
-                 _ptr(g), _stream(), _index64(csr))
+    _dmlc.spmv_t(view, _ptr(d), _ptr(g), _stream())
     return g
 
 
@@ -165,17 +181,11 @@ def spmm(csr: Dict, w: torch.Tensor, bias: Optional[torch.Tensor] = None) -> tor
     not checked on the device.  No atomics and a summation order fixed by k:
     the same inputs give the same bytes."""
     k = _check_dense("w", w, bias)
-    _check(csr, pairs=True)
+    view, nrows = _view(csr, pairs=True)
     _check_device("w", w, csr)
     _check_device("bias", bias, csr)
-    nrows = csr["offset"].numel() - 1
     y = torch.empty((nrows, k), dtype=torch.float32, device=w.device)
-    if _paired(csr):
-        _dmlc.spmm_pairs(_ptr(csr["offset"]), _ptr(csr["index"]), nrows, _ptr(w), _ptr(bias), k,
-                         _ptr(y), _stream())
-    else:
-        _dmlc.spmm(_ptr(csr["offset"]), _ptr(csr["index"]), _ptr(csr.get("value")), nrows, _ptr(w),
-                   _ptr(bias), k, _ptr(y), _stream(), _index64(csr))
+    _dmlc.spmm(view, _ptr(w), _ptr(bias), k, _ptr(y), _stream())
     return y
 
 
@@ -188,14 +198,12 @@ def spmm_t(csr: Dict, d: torch.Tensor, num_features: int) -> torch.Tensor:
     sums are in no fixed order."""
     k = _check_dense("d", d)
     csr = _unpair(csr)
-    _check(csr)
+    view, nrows = _view(csr)
     _check_device("d", d, csr)
-    nrows = csr["offset"].numel() - 1
     if d.shape[0] != nrows:
         raise ValueError(f"d has {d.shape[0]} rows, the CSR {nrows}")
     g = torch.zeros((int(num_features), k), dtype=torch.float32, device=d.device)
-    _dmlc.spmm_t(_ptr(csr["offset"]), _ptr(csr["index"]), _ptr(csr.get("value")), nrows, _ptr(d), k,
-                 _ptr(g), _stream(), _index64(csr))
+    _dmlc.spmm_t(view, _ptr(d), k, _ptr(g), _stream())
     return g
 
 
@@ -221,7 +229,7 @@ def _check_factors(v) -> int:
     return k
 
 
-def _check_fields(name: str, csr: Dict) -> Dict:
+def _check_fields(name: str, csr: Dict) -> None:
     """``csr`` as :func:`ffm` / :func:`ffm_t` take it: a contiguous device CSR
     with one ``field`` per entry, of the index's dtype"""
     if _paired(csr):
@@ -240,7 +248,6 @@ def _check_fields(name: str, csr: Dict) -> Dict:
     if csr.get("value") is not None and csr["value"].numel() != index.numel():
         raise ValueError(f"csr['value'] has {csr['value'].numel()} entries, "
                          f"csr['index'] {index.numel()}")
-    return csr
 
 
 def ffm(csr: Dict, v: torch.Tensor, validate: bool = True) -> torch.Tensor:
@@ -269,14 +276,12 @@ def ffm(csr: Dict, v: torch.Tensor, validate: bool = True) -> torch.Tensor:
     rows re-read global memory.  No atomics, a summation order fixed by the
     row's length and k: the same inputs give the same bytes."""
     k = _check_factors(v)
-    csr = _check_fields("ffm", csr)
+    view, nrows = _view(csr, fields="ffm")
     _check_device("v", v, csr)
-    nrows = csr["offset"].numel() - 1
     y = torch.empty(nrows, dtype=torch.float32, device=v.device)
     err = torch.zeros(1, dtype=torch.int32, device=v.device)
-    _dmlc.ffm_forward(_ptr(csr["offset"]), _ptr(csr["index"]), _ptr(csr.get("value")),
-                      _ptr(csr["field"]), nrows, _ptr(v), int(v.shape[0]), int(v.shape[1]), k,
-                      _ptr(y), _ptr(err), _stream(), _index64(csr))
+    _dmlc.ffm_forward(view, _ptr(v), int(v.shape[0]), int(v.shape[1]), k, _ptr(y), _ptr(err),
+                      _stream())
     if validate:
         bits = int(err.item())
         if bits:
@@ -301,16 +306,14 @@ def ffm_t(csr: Dict, g: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
     if not isinstance(g, torch.Tensor) or g.dim() != 1 or g.dtype != torch.float32 \
             or not g.is_contiguous():
         raise ValueError("g must be a contiguous float32 tensor [rows]")
-    csr = _check_fields("ffm_t", csr)
+    view, nrows = _view(csr, fields="ffm_t")
     _check_device("v", v, csr)
     _check_device("g", g, csr)
-    nrows = csr["offset"].numel() - 1
     if g.numel() != nrows:
         raise ValueError(f"g has {g.numel()} entries, the CSR {nrows} rows")
     dv = torch.zeros_like(v)
-    _dmlc.ffm_backward(_ptr(csr["offset"]), _ptr(csr["index"]), _ptr(csr.get("value")),
-                       _ptr(csr["field"]), nrows, _ptr(g), _ptr(v), int(v.shape[0]),
-                       int(v.shape[1]), k, _ptr(dv), _stream(), _index64(csr))
+    _dmlc.ffm_backward(view, _ptr(g), _ptr(v), int(v.shape[0]), int(v.shape[1]), k, _ptr(dv),
+                       _stream())
     return dv
 
 
@@ -334,16 +337,14 @@ def hashed_dense(csr: Dict, dim: int, seed: int = 0, fp8: bool = True,
     Choose ``scale`` so that the sums stay within +-448.
     """
     csr = _unpair(csr)
-    _check(csr)
-    nrows = csr["offset"].numel() - 1
+    view, nrows = _view(csr)
     dev = csr["index"].device
     if fp8:
         out = torch.empty((nrows, dim), dtype=torch.uint8, device=dev)
     else:
         out = torch.empty((nrows, dim), dtype=torch.float32, device=dev)
-    _dmlc.hashed_dense(_ptr(csr["offset"]), _ptr(csr["index"]), _ptr(csr.get("value")),
-                       _ptr(csr.get("field")), nrows, int(dim), float(scale), int(seed) & 0xFFFFFFFF,
-                       _ptr(out), bool(fp8), _stream(), _index64(csr))
+    _dmlc.hashed_dense(view, int(dim), float(scale), int(seed) & 0xFFFFFFFF, _ptr(out), bool(fp8),
+                       _stream())
     if fp8:
         return out.view(torch.float8_e4m3fn)
     return out
@@ -378,9 +379,9 @@ def transpose(csr: Dict, num_features: int, out: Optional[Dict] = None) -> Dict:
     the outputs (its ``index`` / ``value`` need at least nnz entries).  The
     input may itself be a transpose (its pair views are unpaired first)."""
     csr = _unpair(csr)
-    _check(csr)
+    view, nrows = _view(csr)
     offset, index, value = csr["offset"], csr["index"], csr.get("value")
-    nrows, dev = offset.numel() - 1, index.device
+    dev = index.device
     if num_features <= 0 or num_features > _dmlc.csr_transpose_max_features():
         raise ValueError(f"transpose: num_features must be in (0, "
                          f"{_dmlc.csr_transpose_max_features()}], got {num_features}")
@@ -411,9 +412,8 @@ def transpose(csr: Dict, num_features: int, out: Optional[Dict] = None) -> Dict:
             vals = None
     scratch = _workspace(_dmlc.csr_transpose_scratch_bytes(nnz, num_features), dev)
     err = torch.zeros(1, dtype=torch.int32, device=dev)
-    _dmlc.csr_transpose(_ptr(offset), nrows, lo, nnz, _ptr(index), _ptr(value), int(num_features),
-                        _ptr(col_ptr), _ptr(rows), _ptr(vals), _ptr(scratch), _ptr(err), _stream(),
-                        _index64(csr))
+    _dmlc.csr_transpose(view, lo, nnz, int(num_features), _ptr(col_ptr), _ptr(rows), _ptr(vals),
+                        _ptr(scratch), _ptr(err), _stream())
     if int(err.item()) != 0:
         raise ValueError(f"transpose: a feature id is >= num_features ({num_features})")
     res = {"offset": col_ptr, "index": rows[:nnz],
@@ -508,7 +508,7 @@ def gather_rows(csr: Dict, rows: torch.Tensor, out: Optional[Dict] = None) -> Di
     past a short buffer before the error is raised; the earlier result's
     contents are overwritten either way."""
     csr = _unpair(csr)
-    _check(csr)
+    view, nrows = _view(csr)
     if not isinstance(rows, torch.Tensor) or not rows.is_cuda or not rows.is_contiguous() \
             or rows.dim() != 1:
         raise ValueError("rows must be a 1-D contiguous device tensor")
@@ -520,7 +520,7 @@ def gather_rows(csr: Dict, rows: torch.Tensor, out: Optional[Dict] = None) -> Di
     if field is not None and (not field.is_cuda or not field.is_contiguous()
                               or field.dtype != index.dtype):
         raise ValueError("csr['field'] must be a contiguous device tensor of index's dtype")
-    nrows, n_sel, dev = offset.numel() - 1, rows.numel(), index.device
+    n_sel, dev = rows.numel(), index.device
     cols = _gather_columns(csr, nrows)
     src_entries = min(t.numel() for t in (index, value, field) if t is not None)
     entry_keys = ["index"] + (["value"] if value is not None else []) \
@@ -553,11 +553,9 @@ def gather_rows(csr: Dict, rows: torch.Tensor, out: Optional[Dict] = None) -> Di
                            _ptr(status), _ptr(status) + 8, stream)
 
     def fill(capacity: int) -> None:
-        _dmlc.csr_gather_fill(_ptr(offset), nrows, src_entries, _ptr(rows), rows64, n_sel,
-                              _ptr(bufs["offset"]), _ptr(status), _ptr(index), _ptr(value), _ptr(field),
-                              _ptr(bufs["index"]), _ptr(bufs.get("value")),
-                              _ptr(bufs.get("field")), capacity, _ptr(status) + 8, stream,
-                              _index64(csr))
+        _dmlc.csr_gather_fill(view, src_entries, _ptr(rows), rows64, n_sel, _ptr(bufs["offset"]),
+                              _ptr(status), _ptr(bufs["index"]), _ptr(bufs.get("value")),
+                              _ptr(bufs.get("field")), capacity, _ptr(status) + 8, stream)
 
     if out is None:
         # the read comes between G1 and G2, to size the outputs

@@ -18,6 +18,7 @@
 
 #include "./device_common.h"
 #include "./kernels.h"
+#include "./launch_common.h"
 
 namespace dmlc {
 namespace gpu {
@@ -181,12 +182,6 @@ __global__ __launch_bounds__(kThreads) void k_hashed_dense(
     dev::wave_sync();
   }
 }
-
-int GridFor(size_t work, size_t per_block) {
-  size_t blocks = (work + per_block - 1) / per_block;
-  if (blocks == 0) blocks = 1;
-  return static_cast<int>(blocks < 16384 ? blocks : 16384);
-}
 }  // namespace
 
 void LaunchFill(float* p, size_t n, float v, hipStream_t stream) {
@@ -232,67 +227,66 @@ void LaunchOffsetRebase(const uint64_t* src_offset, size_t nrows, uint64_t src_b
                      src_offset, nrows + 1, src_base, dst_base, dst_offset);
 }
 
-template <typename IndexType>
-void LaunchCSRSpMV(const uint64_t* offset, const IndexType* index, const float* value,
-                   size_t nrows, const float* w, float bias, float* y, hipStream_t stream) {
+void LaunchCSRSpMV(const CsrView& csr, const float* w, float bias, float* y, hipStream_t stream) {
+  CheckView("spmv", csr, true);
+  const size_t nrows = csr.nrows;
   if (nrows == 0) return;
-  // interleaved (index, value) pairs: value is the float after a u32 index
-  if (sizeof(IndexType) == 4 && value != nullptr &&
-      value == reinterpret_cast<const float*>(index) + 1) {
-    CHECK_EQ(reinterpret_cast<uintptr_t>(index) & 7u, 0u) << "spmv: pairs not 8-byte aligned";
+  if (csr.paired) {
     hipLaunchKernelGGL(k_spmv_pairs, dim3(GridFor(nrows, kThreads / kGroup)), dim3(kThreads), 0,
-                       stream, offset, reinterpret_cast<const uint2*>(index), nrows, w, bias, y);
-    return;
+                       stream, csr.offset, static_cast<const uint2*>(csr.index), nrows, w, bias, y);
+  } else {
+    DispatchIndex(csr, [&](auto tag) {
+      using IndexType = decltype(tag);
+      hipLaunchKernelGGL(k_spmv<IndexType>, dim3(GridFor(nrows, kThreads / kGroup)),
+                         dim3(kThreads), 0, stream, csr.offset, IndexOf<IndexType>(csr), csr.value,
+                         nrows, w, bias, y);
+    });
   }
-  hipLaunchKernelGGL(k_spmv<IndexType>, dim3(GridFor(nrows, kThreads / kGroup)), dim3(kThreads),
-                     0, stream, offset, index, value, nrows, w, bias, y);
-}
-
-template <typename IndexType>
-void LaunchCSRSpMVT(const uint64_t* offset, const IndexType* index, const float* value,
-                    size_t nrows, const float* d, float* g, hipStream_t stream) {
-  if (nrows == 0) return;
-  hipLaunchKernelGGL(k_spmvt<IndexType>, dim3(GridFor(nrows, kThreads / kGroup)), dim3(kThreads),
-                     0, stream, offset, index, value, nrows, d, g);
-}
-
-template <typename IndexType>
-void LaunchHashedDenseFP8(const uint64_t* offset, const IndexType* index, const float* value,
-                          const IndexType* field, size_t nrows, int dim, float scale,
-                          uint32_t seed, uint8_t* out, hipStream_t stream) {
-  if (nrows == 0) return;
-  const size_t lds = static_cast<size_t>(dim) * sizeof(float) * (kThreads / dev::kWave);
-  PrepareLdsLaunch(k_hashed_dense<IndexType, true>, lds);
-  hipLaunchKernelGGL((k_hashed_dense<IndexType, true>), dim3(GridFor(nrows, kThreads / dev::kWave)),
-                     dim3(kThreads), lds, stream, offset, index, value, field, nrows, dim, scale,
-                     seed, static_cast<void*>(out));
   DMLC_HIP_CHECK_LAUNCH();
 }
 
-template <typename IndexType>
-void LaunchHashedDenseF32(const uint64_t* offset, const IndexType* index, const float* value,
-                          const IndexType* field, size_t nrows, int dim, uint32_t seed,
-                          float* out, hipStream_t stream) {
+void LaunchCSRSpMVT(const CsrView& csr, const float* d, float* g, hipStream_t stream) {
+  CheckView("spmv_t", csr, false);
+  const size_t nrows = csr.nrows;
   if (nrows == 0) return;
-  const size_t lds = static_cast<size_t>(dim) * sizeof(float) * (kThreads / dev::kWave);
-  PrepareLdsLaunch(k_hashed_dense<IndexType, false>, lds);
-  hipLaunchKernelGGL((k_hashed_dense<IndexType, false>),
-                     dim3(GridFor(nrows, kThreads / dev::kWave)), dim3(kThreads), lds, stream,
-                     offset, index, value, field, nrows, dim, 1.0f, seed, static_cast<void*>(out));
+  DispatchIndex(csr, [&](auto tag) {
+    using IndexType = decltype(tag);
+    hipLaunchKernelGGL(k_spmvt<IndexType>, dim3(GridFor(nrows, kThreads / kGroup)), dim3(kThreads),
+                       0, stream, csr.offset, IndexOf<IndexType>(csr), csr.value, nrows, d, g);
+  });
   DMLC_HIP_CHECK_LAUNCH();
 }
 
-#define DMLC_INSTANTIATE_FEATURE(I)                                                           \
-  template void LaunchCSRSpMV<I>(const uint64_t*, const I*, const float*, size_t, const float*, \
-                                 float, float*, hipStream_t);                                 \
-  template void LaunchCSRSpMVT<I>(const uint64_t*, const I*, const float*, size_t,            \
-                                  const float*, float*, hipStream_t);                         \
-  template void LaunchHashedDenseFP8<I>(const uint64_t*, const I*, const float*, const I*,    \
-                                        size_t, int, float, uint32_t, uint8_t*, hipStream_t); \
-  template void LaunchHashedDenseF32<I>(const uint64_t*, const I*, const float*, const I*,    \
-                                        size_t, int, uint32_t, float*, hipStream_t);
-DMLC_INSTANTIATE_FEATURE(uint32_t)
-DMLC_INSTANTIATE_FEATURE(uint64_t)
+namespace {
+/*! \brief K9 into fp8 (x scale) or f32 rows */
+template <bool kFP8>
+void LaunchHashedDense(const CsrView& csr, int dim, float scale, uint32_t seed, void* out,
+                       hipStream_t stream) {
+  CheckView("hashed_dense", csr, false);
+  const size_t nrows = csr.nrows;
+  if (nrows == 0) return;
+  const size_t lds = static_cast<size_t>(dim) * sizeof(float) * (kThreads / dev::kWave);
+  DispatchIndex(csr, [&](auto tag) {
+    using IndexType = decltype(tag);
+    PrepareLdsLaunch(k_hashed_dense<IndexType, kFP8>, lds);
+    hipLaunchKernelGGL((k_hashed_dense<IndexType, kFP8>),
+                       dim3(GridFor(nrows, kThreads / dev::kWave)), dim3(kThreads), lds, stream,
+                       csr.offset, IndexOf<IndexType>(csr), csr.value, FieldOf<IndexType>(csr),
+                       nrows, dim, scale, seed, out);
+  });
+  DMLC_HIP_CHECK_LAUNCH();
+}
+}  // namespace
+
+void LaunchHashedDenseFP8(const CsrView& csr, int dim, float scale, uint32_t seed, uint8_t* out,
+                          hipStream_t stream) {
+  LaunchHashedDense<true>(csr, dim, scale, seed, out, stream);
+}
+
+void LaunchHashedDenseF32(const CsrView& csr, int dim, uint32_t seed, float* out,
+                          hipStream_t stream) {
+  LaunchHashedDense<false>(csr, dim, 1.0f, seed, out, stream);
+}
 
 }  // namespace gpu
 }  // namespace dmlc

@@ -41,6 +41,7 @@
 
 #include "./device_common.h"
 #include "./kernels.h"
+#include "./launch_common.h"
 
 namespace dmlc {
 namespace gpu {
@@ -52,12 +53,6 @@ constexpr int kGroupsPerBlock = kThreads / kGroup;   // FF1: rows per workgroup
 constexpr int kWavesPerBlock = kThreads / dev::kWave;  // FF2: rows per workgroup
 constexpr uint32_t kSkip = 0xFFFFFFFFu;              // field of an entry that is out of range
 constexpr uint32_t kCap = kFFMStagedRowEntries;
-
-int GridFor(size_t work, size_t per_block) {
-  size_t blocks = (work + per_block - 1) / per_block;
-  if (blocks == 0) blocks = 1;
-  return static_cast<int>(blocks < 16384 ? blocks : 16384);
-}
 
 /*! \brief the entry arrays and the table's extent; Load marks what is out of range */
 template <typename IndexType, bool kHasValue>
@@ -270,62 +265,50 @@ void CheckShape(const char* what, int num_fields, int k) {
       << what << ": k must be a multiple of 4 in [4, " << kFFMMaxRank << "], got " << k;
   CHECK_GE(num_fields, 1) << what << ": num_fields must be >= 1";
 }
-
-bool Aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 }  // namespace
 
-template <typename IndexType>
-void LaunchFFMForward(const uint64_t* offset, const IndexType* index, const float* value,
-                      const IndexType* field, size_t nrows, const float* v, uint64_t features,
-                      int num_fields, int k, float* y, int* error, hipStream_t stream) {
+void LaunchFFMForward(const CsrView& csr, const float* v, uint64_t features, int num_fields, int k,
+                      float* y, int* error, hipStream_t stream) {
+  CheckView("ffm_forward", csr, false);
   CheckShape("ffm_forward", num_fields, k);
   CHECK(Aligned16(v)) << "ffm_forward: v must be 16-byte aligned";
+  const size_t nrows = csr.nrows;
   if (nrows == 0) return;
   const int units = k / 4;
-  int cpr = 1;
-  while (cpr < units) cpr <<= 1;
+  const int cpr = NextPow2(units);
   const dim3 grid(GridFor(nrows, kGroupsPerBlock));
-  const uint64_t nf = static_cast<uint64_t>(num_fields);
-  if (value != nullptr) {
-    hipLaunchKernelGGL((k_ffm_forward<IndexType, true>), grid, dim3(kThreads), 0, stream, offset,
-                       FieldEntries<IndexType, true>{index, field, value, features, nf}, nrows, v,
-                       units, cpr, y, error);
-  } else {
-    hipLaunchKernelGGL((k_ffm_forward<IndexType, false>), grid, dim3(kThreads), 0, stream, offset,
-                       FieldEntries<IndexType, false>{index, field, nullptr, features, nf}, nrows,
-                       v, units, cpr, y, error);
-  }
+  DispatchIndexValue(csr, [&](auto tag, auto has_value) {
+    using IndexType = decltype(tag);
+    constexpr bool kHasValue = decltype(has_value)::value;
+    using Entries = FieldEntries<IndexType, kHasValue>;
+    hipLaunchKernelGGL((k_ffm_forward<IndexType, kHasValue>), grid, dim3(kThreads), 0, stream,
+                       csr.offset,
+                       Entries{IndexOf<IndexType>(csr), FieldOf<IndexType>(csr), csr.value, features,
+                               static_cast<uint64_t>(num_fields)},
+                       nrows, v, units, cpr, y, error);
+  });
   DMLC_HIP_CHECK_LAUNCH();
 }
 
-template <typename IndexType>
-void LaunchFFMBackward(const uint64_t* offset, const IndexType* index, const float* value,
-                       const IndexType* field, size_t nrows, const float* g, const float* v,
-                       uint64_t features, int num_fields, int k, float* dv, hipStream_t stream) {
+void LaunchFFMBackward(const CsrView& csr, const float* g, const float* v, uint64_t features,
+                       int num_fields, int k, float* dv, hipStream_t stream) {
+  CheckView("ffm_backward", csr, false);
   CheckShape("ffm_backward", num_fields, k);
+  const size_t nrows = csr.nrows;
   if (nrows == 0) return;
   const dim3 grid(GridFor(nrows, kWavesPerBlock));
-  const uint64_t nf = static_cast<uint64_t>(num_fields);
-  if (value != nullptr) {
-    hipLaunchKernelGGL((k_ffm_backward<IndexType, true>), grid, dim3(kThreads), 0, stream, offset,
-                       FieldEntries<IndexType, true>{index, field, value, features, nf}, nrows, g, v,
-                       k, dv);
-  } else {
-    hipLaunchKernelGGL((k_ffm_backward<IndexType, false>), grid, dim3(kThreads), 0, stream, offset,
-                       FieldEntries<IndexType, false>{index, field, nullptr, features, nf}, nrows,
-                       g, v, k, dv);
-  }
+  DispatchIndexValue(csr, [&](auto tag, auto has_value) {
+    using IndexType = decltype(tag);
+    constexpr bool kHasValue = decltype(has_value)::value;
+    using Entries = FieldEntries<IndexType, kHasValue>;
+    hipLaunchKernelGGL((k_ffm_backward<IndexType, kHasValue>), grid, dim3(kThreads), 0, stream,
+                       csr.offset,
+                       Entries{IndexOf<IndexType>(csr), FieldOf<IndexType>(csr), csr.value, features,
+                               static_cast<uint64_t>(num_fields)},
+                       nrows, g, v, k, dv);
+  });
   DMLC_HIP_CHECK_LAUNCH();
 }
-
-#define DMLC_INSTANTIATE_FFM(I)                                                                  \
-  template void LaunchFFMForward<I>(const uint64_t*, const I*, const float*, const I*, size_t,   \
-                                    const float*, uint64_t, int, int, float*, int*, hipStream_t); \
-  template void LaunchFFMBackward<I>(const uint64_t*, const I*, const float*, const I*, size_t,  \
-                                     const float*, const float*, uint64_t, int, int, float*,     \
-                                     hipStream_t);
-DMLC_INSTANTIATE_FFM(uint32_t)
-DMLC_INSTANTIATE_FFM(uint64_t)
 
 }  // namespace gpu
 }  // namespace dmlc

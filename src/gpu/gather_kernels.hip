@@ -30,6 +30,7 @@
 
 #include "./device_common.h"
 #include "./kernels.h"
+#include "./launch_common.h"
 
 namespace dmlc {
 namespace gpu {
@@ -244,41 +245,40 @@ void LaunchCSRGatherCount(const uint64_t* offset, uint64_t nrows_src, uint64_t s
   DMLC_HIP_CHECK_LAUNCH();
 }
 
-template <typename IndexType>
-void LaunchCSRGatherFill(const uint64_t* offset, uint64_t nrows_src, uint64_t src_entries,
-                         const void* rows, bool rows64, size_t n_sel, uint64_t* out_offset,
-                         const uint64_t* total, const IndexType* index, const float* value,
-                         const IndexType* field,
-                         IndexType* out_index, float* out_value, IndexType* out_field,
+void LaunchCSRGatherFill(const CsrView& src, uint64_t src_entries, const void* rows, bool rows64,
+                         size_t n_sel, uint64_t* out_offset, const uint64_t* total,
+                         void* out_index, float* out_value, void* out_field,
                          uint64_t out_capacity, uint32_t* error, hipStream_t stream) {
+  CheckView("gather", src, false);
   // the entry count is on the device only: one wave per run of the capacity
   // (waves past the total leave at once), at least the tail's workgroup
   constexpr uint64_t kPerBlock = kGatherRun * kWaves;
   uint64_t blocks = (out_capacity + kPerBlock - 1) / kPerBlock;
   if (blocks == 0) blocks = 1;
   CHECK_LT(blocks, kMaxBlocks) << "gather: out_capacity too large for one launch";
-  if (rows64) {
-    hipLaunchKernelGGL((k_gather_fill<IndexType, int64_t>), dim3(blocks), dim3(kThreads), 0,
-                       stream, offset, nrows_src, src_entries, static_cast<const int64_t*>(rows),
-                       n_sel, out_offset, out_offset + n_sel, total, index, value, field,
-                       out_index, out_value, out_field, out_capacity, error);
-  } else {
-    hipLaunchKernelGGL((k_gather_fill<IndexType, int32_t>), dim3(blocks), dim3(kThreads), 0,
-                       stream, offset, nrows_src, src_entries, static_cast<const int32_t*>(rows),
-                       n_sel, out_offset, out_offset + n_sel, total, index, value, field,
-                       out_index, out_value, out_field, out_capacity, error);
-  }
+  const uint64_t nrows_src = src.nrows;
+  DispatchIndex(src, [&](auto tag) {
+    using IndexType = decltype(tag);
+    const IndexType* index = IndexOf<IndexType>(src);
+    const IndexType* field = FieldOf<IndexType>(src);
+    IndexType* oindex = static_cast<IndexType*>(out_index);
+    IndexType* ofield = static_cast<IndexType*>(out_field);
+    if (rows64) {
+      hipLaunchKernelGGL((k_gather_fill<IndexType, int64_t>), dim3(blocks), dim3(kThreads), 0,
+                         stream, src.offset, nrows_src, src_entries,
+                         static_cast<const int64_t*>(rows), n_sel, out_offset, out_offset + n_sel,
+                         total, index, src.value, field, oindex, out_value, ofield, out_capacity,
+                         error);
+    } else {
+      hipLaunchKernelGGL((k_gather_fill<IndexType, int32_t>), dim3(blocks), dim3(kThreads), 0,
+                         stream, src.offset, nrows_src, src_entries,
+                         static_cast<const int32_t*>(rows), n_sel, out_offset, out_offset + n_sel,
+                         total, index, src.value, field, oindex, out_value, ofield, out_capacity,
+                         error);
+    }
+  });
   DMLC_HIP_CHECK_LAUNCH();
 }
-
-#define DMLC_INSTANTIATE_GATHER(I)                                                              \
-  template void LaunchCSRGatherFill<I>(const uint64_t*, uint64_t, uint64_t, const void*, bool,  \
-                                       size_t, uint64_t*, const uint64_t*, const I*, const float*,      \
-                                       const I*, I*, float*, I*, uint64_t, uint32_t*,           \
-                                       hipStream_t);
-DMLC_INSTANTIATE_GATHER(uint32_t)
-DMLC_INSTANTIATE_GATHER(uint64_t)
-#undef DMLC_INSTANTIATE_GATHER
 
 }  // namespace gpu
 }  // namespace dmlc

@@ -15,12 +15,16 @@
  *   K10 csr concat       LaunchCSRAppend          (feature_kernels.hip)
  *   K11 spmv / sdot      LaunchCSRSpMV, LaunchCSRSpMVT (feature_kernels.hip)
  *   M1 spmm              LaunchCSRSpMM            (spmm_kernels.hip)
- *   M1p spmm over pairs  LaunchCSRSpMMPairs       (spmm_kernels.hip)
+ *   M1p spmm over pairs  LaunchCSRSpMM, CsrView::paired
  *   M2 spmm transposed   LaunchCSRSpMMT           (spmm_kernels.hip)
  *   FF1 ffm forward      LaunchFFMForward         (ffm_kernels.hip)
  *   FF2 ffm backward     LaunchFFMBackward        (ffm_kernels.hip)
  *   G1 row gather count  LaunchCSRGatherCount     (gather_kernels.hip)
  *   G2 row gather fill   LaunchCSRGatherFill      (gather_kernels.hip)
+ *   CSR -> CSC           LaunchCSRTranspose       (transpose_kernels.hip)
+ * The launchers of K9, K11, M1 / M2, FF1 / FF2, G2 and the transpose take
+ * their CSR operand as one CsrView and pick the kernel for its index width
+ * (and pair layout) themselves; launch_common.h holds what they share.
  * All launchers are asynchronous on `stream` and never allocate or
  * synchronise (graph-capture safe, cdna_hip_programming.md Guideline 9).
  */
@@ -85,6 +89,22 @@ constexpr int kMaxPartialBlocks = 8192;
 /*! \brief fold nblocks MetaPartial slots into meta (max / or) with one workgroup */
 void LaunchReducePartials(const MetaPartial* partials, int nblocks, ChunkMeta* meta,
                           hipStream_t stream);
+
+/*!
+ * \brief the device CSR operand of the op launchers (K9, K11, M1 / M2, FF1 /
+ *  FF2, G2, transpose).  Every launcher checks its view before anything else,
+ *  an empty one included: `paired` needs !index64, value == (float*)index + 1
+ *  and 8-byte aligned pairs, and only LaunchCSRSpMV / LaunchCSRSpMM take it.
+ */
+struct CsrView {
+  const uint64_t* offset;  // nrows + 1, may be a slice (offset[0] != 0)
+  const void* index;       // u32 or u64 per index64
+  const float* value;      // may be null (1.0 per entry)
+  const void* field;       // may be null; index's type
+  size_t nrows;
+  bool index64;
+  bool paired;             // index/value are the interleaved (u32, f32) pairs of a transpose
+};
 
 /*! \brief destination arrays of the fill pass (device pointers) */
 template <typename IndexType>
@@ -374,15 +394,11 @@ void LaunchRecordIOGather(const uint8_t* src, const uint64_t* src_off, const uin
  *  torch's float8_e4m3fn cast), a NaN gives 0xFF whatever its sign (torch:
  *  0x7F for a positive NaN).
  */
-template <typename IndexType>
-void LaunchHashedDenseFP8(const uint64_t* offset, const IndexType* index, const float* value,
-                          const IndexType* field, size_t nrows, int dim, float scale,
-                          uint32_t seed, uint8_t* out, hipStream_t stream);
+void LaunchHashedDenseFP8(const CsrView& csr, int dim, float scale, uint32_t seed, uint8_t* out,
+                          hipStream_t stream);
 /*! \brief same but f32 output (reference for the fp8 path / bf16 consumers) */
-template <typename IndexType>
-void LaunchHashedDenseF32(const uint64_t* offset, const IndexType* index, const float* value,
-                          const IndexType* field, size_t nrows, int dim, uint32_t seed,
-                          float* out, hipStream_t stream);
+void LaunchHashedDenseF32(const CsrView& csr, int dim, uint32_t seed, float* out,
+                          hipStream_t stream);
 /*!
  * \brief K9 fused with the text walk (BASELINE config 5): every valid line of a
  *  LibSVM / LibFM chunk becomes row row_base + (line_info >> 32) of a dense
@@ -398,15 +414,11 @@ void LaunchTextHashed(const char* text, size_t nbytes, const uint32_t* line_star
                       TextFormat format, const uint64_t* line_info, uint64_t row_base, int dim,
                       float scale, uint32_t seed, bool fp8, void* out, float* labels,
                       MetaPartial* partials, ChunkMeta* meta, hipStream_t stream);
-/*! \brief K11: y[r] = sum_j value * w[index] (+ bias), 16 lanes per row; value ==
- *  (float*)index + 1 (u32 indices): interleaved (index, value) pairs */
-template <typename IndexType>
-void LaunchCSRSpMV(const uint64_t* offset, const IndexType* index, const float* value,
-                   size_t nrows, const float* w, float bias, float* y, hipStream_t stream);
+/*! \brief K11: y[r] = sum_j value * w[index] (+ bias), 16 lanes per row; a
+ *  paired view is read as interleaved (index, value) pairs */
+void LaunchCSRSpMV(const CsrView& csr, const float* w, float bias, float* y, hipStream_t stream);
 /*! \brief K11^T: g[index] += value * d[r] (f32 atomics) */
-template <typename IndexType>
-void LaunchCSRSpMVT(const uint64_t* offset, const IndexType* index, const float* value,
-                    size_t nrows, const float* d, float* g, hipStream_t stream);
+void LaunchCSRSpMVT(const CsrView& csr, const float* d, float* g, hipStream_t stream);
 // ------------------------- SpMM (spmm_kernels.hip) -------------------------
 /*! \brief widest dense operand (columns) of M1 / M1p / M2 */
 constexpr int kSpMMMaxCols = 256;
@@ -419,22 +431,16 @@ constexpr int kSpMMMaxCols = 256;
  *  and bias takes 16-byte loads, anything else 4-byte loads.  No atomics and a
  *  summation order fixed by k: the output bytes are a pure function of the
  *  inputs.  Feature ids must be < features (not checked on the device).
+ *  M1p (a paired view): M1 over the interleaved (u32 index, f32 value) pairs
+ *  of a transpose, one 8-byte load per entry; the same summation order as M1.
+ *  A row of any length runs on one lane group of one wave.
  */
-template <typename IndexType>
-void LaunchCSRSpMM(const uint64_t* offset, const IndexType* index, const float* value,
-                   size_t nrows, const float* w, const float* bias, int k, float* y,
+void LaunchCSRSpMM(const CsrView& csr, const float* w, const float* bias, int k, float* y,
                    hipStream_t stream);
-/*! \brief M1p: M1 over the interleaved (u32 index, f32 value) pairs of a
- *  transpose, one 8-byte load per entry; the same summation order as M1.  A
- *  row of any length runs on one lane group of one wave. */
-void LaunchCSRSpMMPairs(const uint64_t* offset, const void* pairs, size_t nrows, const float* w,
-                        const float* bias, int k, float* y, hipStream_t stream);
 /*! \brief M2: g[index[j], :] += value[j] * d[r, :] with no-return f32 atomics
  *  into a zeroed g [features x k]; the lanes of one entry cover one contiguous
  *  4 * min(k, 64)-byte segment of a g row per wave-instruction */
-template <typename IndexType>
-void LaunchCSRSpMMT(const uint64_t* offset, const IndexType* index, const float* value,
-                    size_t nrows, const float* d, int k, float* g, hipStream_t stream);
+void LaunchCSRSpMMT(const CsrView& csr, const float* d, int k, float* g, hipStream_t stream);
 // -------------------- field-aware FM (ffm_kernels.hip) ---------------------
 /*! \brief largest factor rank k of FF1 / FF2 (k: a multiple of 4 from 4) */
 constexpr int kFFMMaxRank = 32;
@@ -453,10 +459,8 @@ constexpr uint32_t kFFMErrIndex = 1, kFFMErrField = 2;
  *  kFFMErrIndex / kFFMErrField into *error (an int32 the caller zeroed).  No
  *  atomics on y; the summation order depends on the row's length and k alone.
  */
-template <typename IndexType>
-void LaunchFFMForward(const uint64_t* offset, const IndexType* index, const float* value,
-                      const IndexType* field, size_t nrows, const float* v, uint64_t features,
-                      int num_fields, int k, float* y, int* error, hipStream_t stream);
+void LaunchFFMForward(const CsrView& csr, const float* v, uint64_t features, int num_fields, int k,
+                      float* y, int* error, hipStream_t stream);
 /*!
  * \brief FF2: dv[i_a, f_b, :] += g[r] x_a x_b v[i_b, f_a, :] for every ordered
  *  pair a != b of every row, with no-return f32 atomics into a zeroed dv shaped
@@ -465,10 +469,8 @@ void LaunchFFMForward(const uint64_t* offset, const IndexType* index, const floa
  *  contiguous stretch of dv[i_a, :, :].  Rows with g[r] == +-0 are skipped;
  *  out-of-range entries are skipped as in FF1 (nothing is reported here).
  */
-template <typename IndexType>
-void LaunchFFMBackward(const uint64_t* offset, const IndexType* index, const float* value,
-                       const IndexType* field, size_t nrows, const float* g, const float* v,
-                       uint64_t features, int num_fields, int k, float* dv, hipStream_t stream);
+void LaunchFFMBackward(const CsrView& csr, const float* g, const float* v, uint64_t features,
+                       int num_fields, int k, float* dv, hipStream_t stream);
 // ------------------------ HashedFM (fm_kernels.hip) ------------------------
 /*! \brief factor rank of the HIP HashedFM kernels and the [w | V] column count */
 constexpr int kFmRank = 16;
@@ -532,8 +534,8 @@ void LaunchOffsetRebase(const uint64_t* src_offset, size_t nrows, uint64_t src_b
 void LaunchPageRebase(uint64_t* offset, size_t nrows, const uint64_t* page_row_end,
                       const uint64_t* page_nnz_base, int npages, hipStream_t stream);
 /*!
- * \brief CSR -> CSC (transpose_kernels.hip): rows [0, nrows) of a CSR whose
- *  entries are [base, base + nnz) of index / value; writes col_ptr
+ * \brief CSR -> CSC (transpose_kernels.hip): the rows of csr, whose entries
+ *  are [base, base + nnz) of its index / value; writes col_ptr
  *  [num_features + 1] (u64, from 0), row_out [nnz] (u32 row ids, ascending
  *  within each column) and val_out [nnz] (when value != null).  With
  *  val_out == (float*)row_out + 1 (row_out 8-byte aligned) the output is
@@ -542,9 +544,7 @@ void LaunchPageRebase(uint64_t* offset, size_t nrows, const uint64_t* page_row_e
  *  num_features <= CSRTransposeMaxFeatures(); scratch of
  *  CSRTransposeScratchBytes(nnz, num_features) bytes (256-byte aligned).
  */
-template <typename IndexType>
-void LaunchCSRTranspose(const uint64_t* offset, size_t nrows, uint64_t base, uint64_t nnz,
-                        const IndexType* index, const float* value, uint64_t num_features,
+void LaunchCSRTranspose(const CsrView& csr, uint64_t base, uint64_t nnz, uint64_t num_features,
                         uint64_t* col_ptr, uint32_t* row_out, float* val_out, void* scratch,
                         uint32_t* error, hipStream_t stream);
 size_t CSRTransposeScratchBytes(uint64_t nnz, uint64_t num_features);
@@ -576,11 +576,13 @@ void LaunchCSRGatherCount(const uint64_t* offset, uint64_t nrows_src, uint64_t s
                           float* out_label, float* out_weight, uint64_t* out_qid, uint32_t* error,
                           hipStream_t stream);
 /*!
- * \brief G2: the entries of every selected row to their place in the batch:
+ * \brief G2: the entries of every selected row of src (G1's offset, nrows_src
+ *  = src.nrows) to their place in the batch:
  *  out_*[p] = *[offset[rows[i]] + p - out_offset[i]] for out_offset[i] <= p <
  *  out_offset[i + 1] (index, and value / field when non-null: a missing
- *  column stays missing).  out_offset: G1's lengths scanned (n_sel + 1 slots;
- *  the closing one is written here from *total, the scan's device total).  A
+ *  column stays missing; out_index / out_field have src's index type).
+ *  out_offset: G1's lengths scanned (n_sel + 1 slots; the closing one is
+ *  written here from *total, the scan's device total).  A
  *  wave owns CSRGatherRunEntries() consecutive output entries.  Positions at
  *  or past out_capacity (entries of out_*) are not written and set
  *  kGatherErrCapacity; the launch is sized by out_capacity, the total being
@@ -588,12 +590,9 @@ void LaunchCSRGatherCount(const uint64_t* offset, uint64_t nrows_src, uint64_t s
  *  row pointer changed after G1 checked it) is not read and sets
  *  kGatherErrSource.  No atomics on the outputs.
  */
-template <typename IndexType>
-void LaunchCSRGatherFill(const uint64_t* offset, uint64_t nrows_src, uint64_t src_entries,
-                         const void* rows, bool rows64, size_t n_sel, uint64_t* out_offset,
-                         const uint64_t* total, const IndexType* index, const float* value,
-                         const IndexType* field,
-                         IndexType* out_index, float* out_value, IndexType* out_field,
+void LaunchCSRGatherFill(const CsrView& src, uint64_t src_entries, const void* rows, bool rows64,
+                         size_t n_sel, uint64_t* out_offset, const uint64_t* total,
+                         void* out_index, float* out_value, void* out_field,
                          uint64_t out_capacity, uint32_t* error, hipStream_t stream);
 /*! \brief fill n floats with v */
 void LaunchFill(float* p, size_t n, float v, hipStream_t stream);

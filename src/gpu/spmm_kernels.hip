@@ -30,18 +30,13 @@
 
 #include "./device_common.h"
 #include "./kernels.h"
+#include "./launch_common.h"
 
 namespace dmlc {
 namespace gpu {
 
 namespace {
 constexpr int kThreads = 256;
-
-int GridFor(size_t work, size_t per_block) {
-  size_t blocks = (work + per_block - 1) / per_block;
-  if (blocks == 0) blocks = 1;
-  return static_cast<int>(blocks < 16384 ? blocks : 16384);
-}
 
 /*! \brief entries of a CSR with separate index / value arrays */
 template <typename IndexType, bool kHasValue>
@@ -160,19 +155,11 @@ __global__ __launch_bounds__(kThreads) void k_spmm_t(const uint64_t* __restrict_
   }
 }
 
-int NextPow2(int v) {
-  int p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
-
 /*! \brief lanes per entry and lanes per row for `units` units per row */
 void Layout(int units, int* cpr, int* group) {
   *cpr = NextPow2(units) < dev::kWave ? NextPow2(units) : dev::kWave;
   *group = 4 * *cpr < 16 ? 16 : (4 * *cpr > dev::kWave ? dev::kWave : 4 * *cpr);
 }
-
-bool Aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 template <typename Entries>
 void LaunchSpMM(const uint64_t* offset, const Entries& src, size_t nrows, const float* w,
@@ -194,48 +181,40 @@ void LaunchSpMM(const uint64_t* offset, const Entries& src, size_t nrows, const 
 }
 }  // namespace
 
-template <typename IndexType>
-void LaunchCSRSpMM(const uint64_t* offset, const IndexType* index, const float* value,
-                   size_t nrows, const float* w, const float* bias, int k, float* y,
+void LaunchCSRSpMM(const CsrView& csr, const float* w, const float* bias, int k, float* y,
                    hipStream_t stream) {
-  if (value != nullptr) {
-    LaunchSpMM(offset, CsrEntries<IndexType, true>{index, value}, nrows, w, bias, k, y, stream);
-  } else {
-    LaunchSpMM(offset, CsrEntries<IndexType, false>{index, nullptr}, nrows, w, bias, k, y, stream);
+  CheckView("spmm", csr, true);
+  if (csr.paired) {
+    LaunchSpMM(csr.offset, PairEntries{static_cast<const uint2*>(csr.index)}, csr.nrows, w, bias,
+               k, y, stream);
+    return;
   }
+  DispatchIndexValue(csr, [&](auto tag, auto has_value) {
+    using IndexType = decltype(tag);
+    using Entries = CsrEntries<IndexType, decltype(has_value)::value>;
+    LaunchSpMM(csr.offset, Entries{IndexOf<IndexType>(csr), csr.value}, csr.nrows, w, bias, k, y,
+               stream);
+  });
 }
 
-void LaunchCSRSpMMPairs(const uint64_t* offset, const void* pairs, size_t nrows, const float* w,
-                        const float* bias, int k, float* y, hipStream_t stream) {
-  CHECK_EQ(reinterpret_cast<uintptr_t>(pairs) & 7u, 0u) << "spmm: pairs not 8-byte aligned";
-  LaunchSpMM(offset, PairEntries{static_cast<const uint2*>(pairs)}, nrows, w, bias, k, y, stream);
-}
-
-template <typename IndexType>
-void LaunchCSRSpMMT(const uint64_t* offset, const IndexType* index, const float* value,
-                    size_t nrows, const float* d, int k, float* g, hipStream_t stream) {
+void LaunchCSRSpMMT(const CsrView& csr, const float* d, int k, float* g, hipStream_t stream) {
+  CheckView("spmm_t", csr, false);
   CHECK(k >= 1 && k <= kSpMMMaxCols) << "spmm_t: k must be in [1, " << kSpMMMaxCols << "], got " << k;
+  const size_t nrows = csr.nrows;
   if (nrows == 0) return;
   int cpr, group;
   Layout(k, &cpr, &group);
   const dim3 grid(GridFor(nrows, kThreads / group));
-  if (value != nullptr) {
-    hipLaunchKernelGGL((k_spmm_t<IndexType, true>), grid, dim3(kThreads), 0, stream, offset,
-                       CsrEntries<IndexType, true>{index, value}, nrows, d, k, cpr, group, g);
-  } else {
-    hipLaunchKernelGGL((k_spmm_t<IndexType, false>), grid, dim3(kThreads), 0, stream, offset,
-                       CsrEntries<IndexType, false>{index, nullptr}, nrows, d, k, cpr, group, g);
-  }
+  DispatchIndexValue(csr, [&](auto tag, auto has_value) {
+    using IndexType = decltype(tag);
+    constexpr bool kHasValue = decltype(has_value)::value;
+    using Entries = CsrEntries<IndexType, kHasValue>;
+    hipLaunchKernelGGL((k_spmm_t<IndexType, kHasValue>), grid, dim3(kThreads), 0, stream,
+                       csr.offset, Entries{IndexOf<IndexType>(csr), csr.value}, nrows, d, k, cpr,
+                       group, g);
+  });
   DMLC_HIP_CHECK_LAUNCH();
 }
-
-#define DMLC_INSTANTIATE_SPMM(I)                                                                \
-  template void LaunchCSRSpMM<I>(const uint64_t*, const I*, const float*, size_t, const float*, \
-                                 const float*, int, float*, hipStream_t);                       \
-  template void LaunchCSRSpMMT<I>(const uint64_t*, const I*, const float*, size_t,              \
-                                  const float*, int, float*, hipStream_t);
-DMLC_INSTANTIATE_SPMM(uint32_t)
-DMLC_INSTANTIATE_SPMM(uint64_t)
 
 }  // namespace gpu
 }  // namespace dmlc

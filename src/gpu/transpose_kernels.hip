@@ -47,6 +47,7 @@
 
 #include "./device_common.h"
 #include "./kernels.h"
+#include "./launch_common.h"
 
 namespace dmlc {
 namespace gpu {
@@ -958,55 +959,54 @@ size_t CSRTransposeScratchBytes(uint64_t nnz, uint64_t num_features) {
 
 uint64_t CSRTransposeMaxFeatures() { return static_cast<uint64_t>(kMaxBuckets) << kMaxBits3; }
 
-template <typename IndexType>
-void LaunchCSRTranspose(const uint64_t* offset, size_t nrows, uint64_t base, uint64_t nnz,
-                        const IndexType* index, const float* value, uint64_t num_features,
+void LaunchCSRTranspose(const CsrView& csr, uint64_t base, uint64_t nnz, uint64_t num_features,
                         uint64_t* col_ptr, uint32_t* row_out, float* val_out, void* scratch,
                         uint32_t* error, hipStream_t stream) {
+  CheckView("transpose", csr, false);
+  const size_t nrows = csr.nrows;
   CHECK_GT(num_features, 0U);
   CHECK_LE(num_features, CSRTransposeMaxFeatures()) << "transpose: num_features above the limit";
   CHECK_LT(nnz, uint64_t(1) << 32) << "transpose: at most 2^32 - 1 entries";
   CHECK_LT(nrows, size_t(1) << 32) << "transpose: at most 2^32 - 1 rows";
   const TransposePlan p = Plan(nnz, num_features);
-  if (p.three) {
+  DispatchIndex(csr, [&](auto tag) {
+    using IndexType = decltype(tag);
+    const uint64_t* offset = csr.offset;
+    const IndexType* index = IndexOf<IndexType>(csr);
+    const float* value = csr.value;
+    if (p.three) {
+      switch (p.low_bits) {
+        case 16:
+          RunSort3<IndexType, 16>(p, offset, nrows, base, nnz, index, value, num_features, col_ptr,
+                                  row_out, val_out, scratch, error, stream);
+          break;
+        case 17:
+          RunSort3<IndexType, 17>(p, offset, nrows, base, nnz, index, value, num_features, col_ptr,
+                                  row_out, val_out, scratch, error, stream);
+          break;
+        default:
+          RunSort3<IndexType, 18>(p, offset, nrows, base, nnz, index, value, num_features, col_ptr,
+                                  row_out, val_out, scratch, error, stream);
+          break;
+      }
+      return;
+    }
     switch (p.low_bits) {
-      case 16:
-        RunSort3<IndexType, 16>(p, offset, nrows, base, nnz, index, value, num_features, col_ptr,
-                                row_out, val_out, scratch, error, stream);
+      case 10:
+        RunSort<IndexType, 10>(p, offset, nrows, base, nnz, index, value, num_features, col_ptr,
+                               row_out, val_out, scratch, error, stream);
         break;
-      case 17:
-        RunSort3<IndexType, 17>(p, offset, nrows, base, nnz, index, value, num_features, col_ptr,
-                                row_out, val_out, scratch, error, stream);
+      case 11:
+        RunSort<IndexType, 11>(p, offset, nrows, base, nnz, index, value, num_features, col_ptr,
+                               row_out, val_out, scratch, error, stream);
         break;
       default:
-        RunSort3<IndexType, 18>(p, offset, nrows, base, nnz, index, value, num_features, col_ptr,
-                                row_out, val_out, scratch, error, stream);
+        RunSort<IndexType, 12>(p, offset, nrows, base, nnz, index, value, num_features, col_ptr,
+                               row_out, val_out, scratch, error, stream);
         break;
     }
-    return;
-  }
-  switch (p.low_bits) {
-    case 10:
-      RunSort<IndexType, 10>(p, offset, nrows, base, nnz, index, value, num_features, col_ptr,
-                             row_out, val_out, scratch, error, stream);
-      break;
-    case 11:
-      RunSort<IndexType, 11>(p, offset, nrows, base, nnz, index, value, num_features, col_ptr,
-                             row_out, val_out, scratch, error, stream);
-      break;
-    default:
-      RunSort<IndexType, 12>(p, offset, nrows, base, nnz, index, value, num_features, col_ptr,
-                             row_out, val_out, scratch, error, stream);
-      break;
-  }
+  });
 }
-
-template void LaunchCSRTranspose<uint32_t>(const uint64_t*, size_t, uint64_t, uint64_t,
-                                           const uint32_t*, const float*, uint64_t, uint64_t*,
-                                           uint32_t*, float*, void*, uint32_t*, hipStream_t);
-template void LaunchCSRTranspose<uint64_t>(const uint64_t*, size_t, uint64_t, uint64_t,
-                                           const uint64_t*, const float*, uint64_t, uint64_t*,
-                                           uint32_t*, float*, void*, uint32_t*, hipStream_t);
 
 }  // namespace gpu
 }  // namespace dmlc

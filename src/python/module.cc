@@ -28,6 +28,7 @@
 
 #include <memory>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../gpu/kernels.h"
@@ -752,6 +753,24 @@ py::bytes UnpackTextDevicePy(const std::string& packed, size_t dst_offset, size_
   return py::bytes(out);
 }
 
+// ------------------------------------------------------------- op operands
+/*! \brief a device address handed over as an integer (tensor.data_ptr(); 0: none) */
+template <typename T>
+T* Ptr(uintptr_t p) {
+  return reinterpret_cast<T*>(p);
+}
+
+/*! \brief the CSR operand of an op as ops._describe packs it:
+ *  (offset, index, value, field, nrows, index64, paired) */
+using CsrArg = std::tuple<uintptr_t, uintptr_t, uintptr_t, uintptr_t, size_t, bool, bool>;
+
+gpu::CsrView View(const CsrArg& a) {
+  return gpu::CsrView{Ptr<const uint64_t>(std::get<0>(a)), Ptr<const void>(std::get<1>(a)),
+                      Ptr<const float>(std::get<2>(a)),    Ptr<const void>(std::get<3>(a)),
+                      std::get<4>(a),                      std::get<5>(a),
+                      std::get<6>(a)};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_dmlc, m) {
@@ -903,171 +922,67 @@ PYBIND11_MODULE(_dmlc, m) {
         "sub-shard visiting order of InputSplitShuffle in a given epoch");
   m.def(
       "spmv",
-      [stream_of](uintptr_t offset, uintptr_t index, uintptr_t value, size_t nrows, uintptr_t w,
-                  float bias, uintptr_t y, uintptr_t stream, bool index64) {
-        auto* off = reinterpret_cast<const uint64_t*>(offset);
-        auto* val = reinterpret_cast<const float*>(value);
-        if (index64) {
-          gpu::LaunchCSRSpMV<uint64_t>(off, reinterpret_cast<const uint64_t*>(index), val, nrows,
-                                       reinterpret_cast<const float*>(w), bias,
-                                       reinterpret_cast<float*>(y), stream_of(stream));
-        } else {
-          gpu::LaunchCSRSpMV<uint32_t>(off, reinterpret_cast<const uint32_t*>(index), val, nrows,
-                                       reinterpret_cast<const float*>(w), bias,
-                                       reinterpret_cast<float*>(y), stream_of(stream));
-        }
+      [stream_of](const CsrArg& csr, uintptr_t w, float bias, uintptr_t y, uintptr_t stream) {
+        gpu::LaunchCSRSpMV(View(csr), Ptr<const float>(w), bias, Ptr<float>(y), stream_of(stream));
       },
-      py::arg("offset"), py::arg("index"), py::arg("value"), py::arg("nrows"), py::arg("w"),
-      py::arg("bias"), py::arg("y"), py::arg("stream"), py::arg("index64") = false);
+      py::arg("csr"), py::arg("w"), py::arg("bias"), py::arg("y"), py::arg("stream"));
   m.def(
       "spmv_t",
-      [stream_of](uintptr_t offset, uintptr_t index, uintptr_t value, size_t nrows, uintptr_t d,
-                  uintptr_t g, uintptr_t stream, bool index64) {
-        auto* off = reinterpret_cast<const uint64_t*>(offset);
-        auto* val = reinterpret_cast<const float*>(value);
-        if (index64) {
-          gpu::LaunchCSRSpMVT<uint64_t>(off, reinterpret_cast<const uint64_t*>(index), val, nrows,
-                                        reinterpret_cast<const float*>(d),
-                                        reinterpret_cast<float*>(g), stream_of(stream));
-        } else {
-          gpu::LaunchCSRSpMVT<uint32_t>(off, reinterpret_cast<const uint32_t*>(index), val, nrows,
-                                        reinterpret_cast<const float*>(d),
-                                        reinterpret_cast<float*>(g), stream_of(stream));
-        }
+      [stream_of](const CsrArg& csr, uintptr_t d, uintptr_t g, uintptr_t stream) {
+        gpu::LaunchCSRSpMVT(View(csr), Ptr<const float>(d), Ptr<float>(g), stream_of(stream));
       },
-      py::arg("offset"), py::arg("index"), py::arg("value"), py::arg("nrows"), py::arg("d"),
-      py::arg("g"), py::arg("stream"), py::arg("index64") = false);
+      py::arg("csr"), py::arg("d"), py::arg("g"), py::arg("stream"));
   m.def(
       "spmm",
-      [stream_of](uintptr_t offset, uintptr_t index, uintptr_t value, size_t nrows, uintptr_t w,
-                  uintptr_t bias, int k, uintptr_t y, uintptr_t stream, bool index64) {
-        auto* off = reinterpret_cast<const uint64_t*>(offset);
-        auto* val = reinterpret_cast<const float*>(value);
-        if (index64) {
-          gpu::LaunchCSRSpMM<uint64_t>(off, reinterpret_cast<const uint64_t*>(index), val, nrows,
-                                       reinterpret_cast<const float*>(w),
-                                       reinterpret_cast<const float*>(bias), k,
-                                       reinterpret_cast<float*>(y), stream_of(stream));
-        } else {
-          gpu::LaunchCSRSpMM<uint32_t>(off, reinterpret_cast<const uint32_t*>(index), val, nrows,
-                                       reinterpret_cast<const float*>(w),
-                                       reinterpret_cast<const float*>(bias), k,
-                                       reinterpret_cast<float*>(y), stream_of(stream));
-        }
+      [stream_of](const CsrArg& csr, uintptr_t w, uintptr_t bias, int k, uintptr_t y,
+                  uintptr_t stream) {
+        gpu::LaunchCSRSpMM(View(csr), Ptr<const float>(w), Ptr<const float>(bias), k,
+                           Ptr<float>(y), stream_of(stream));
       },
-      py::arg("offset"), py::arg("index"), py::arg("value"), py::arg("nrows"), py::arg("w"),
-      py::arg("bias"), py::arg("k"), py::arg("y"), py::arg("stream"), py::arg("index64") = false);
-  m.def(
-      "spmm_pairs",
-      [stream_of](uintptr_t offset, uintptr_t pairs, size_t nrows, uintptr_t w, uintptr_t bias,
-                  int k, uintptr_t y, uintptr_t stream) {
-        gpu::LaunchCSRSpMMPairs(reinterpret_cast<const uint64_t*>(offset),
-                                reinterpret_cast<const void*>(pairs), nrows,
-                                reinterpret_cast<const float*>(w),
-                                reinterpret_cast<const float*>(bias), k,
-                                reinterpret_cast<float*>(y), stream_of(stream));
-      },
-      py::arg("offset"), py::arg("pairs"), py::arg("nrows"), py::arg("w"), py::arg("bias"),
-      py::arg("k"), py::arg("y"), py::arg("stream"));
+      py::arg("csr"), py::arg("w"), py::arg("bias"), py::arg("k"), py::arg("y"),
+      py::arg("stream"));
   m.def(
       "spmm_t",
-      [stream_of](uintptr_t offset, uintptr_t index, uintptr_t value, size_t nrows, uintptr_t d,
-                  int k, uintptr_t g, uintptr_t stream, bool index64) {
-        auto* off = reinterpret_cast<const uint64_t*>(offset);
-        auto* val = reinterpret_cast<const float*>(value);
-        if (index64) {
-          gpu::LaunchCSRSpMMT<uint64_t>(off, reinterpret_cast<const uint64_t*>(index), val, nrows,
-                                        reinterpret_cast<const float*>(d), k,
-                                        reinterpret_cast<float*>(g), stream_of(stream));
-        } else {
-          gpu::LaunchCSRSpMMT<uint32_t>(off, reinterpret_cast<const uint32_t*>(index), val, nrows,
-                                        reinterpret_cast<const float*>(d), k,
-                                        reinterpret_cast<float*>(g), stream_of(stream));
-        }
+      [stream_of](const CsrArg& csr, uintptr_t d, int k, uintptr_t g, uintptr_t stream) {
+        gpu::LaunchCSRSpMMT(View(csr), Ptr<const float>(d), k, Ptr<float>(g), stream_of(stream));
       },
-      py::arg("offset"), py::arg("index"), py::arg("value"), py::arg("nrows"), py::arg("d"),
-      py::arg("k"), py::arg("g"), py::arg("stream"), py::arg("index64") = false);
+      py::arg("csr"), py::arg("d"), py::arg("k"), py::arg("g"), py::arg("stream"));
   m.def("spmm_max_cols", []() { return gpu::kSpMMMaxCols; },
         "widest dense operand (columns) ops.spmm / ops.spmm_t take");
   m.def(
       "ffm_forward",
-      [stream_of](uintptr_t offset, uintptr_t index, uintptr_t value, uintptr_t field, size_t nrows,
-                  uintptr_t v, uint64_t features, int num_fields, int k, uintptr_t y,
-                  uintptr_t error, uintptr_t stream, bool index64) {
-        auto* off = reinterpret_cast<const uint64_t*>(offset);
-        auto* val = reinterpret_cast<const float*>(value);
-        if (index64) {
-          gpu::LaunchFFMForward<uint64_t>(off, reinterpret_cast<const uint64_t*>(index), val,
-                                          reinterpret_cast<const uint64_t*>(field), nrows,
-                                          reinterpret_cast<const float*>(v), features, num_fields, k,
-                                          reinterpret_cast<float*>(y),
-                                          reinterpret_cast<int*>(error), stream_of(stream));
-        } else {
-          gpu::LaunchFFMForward<uint32_t>(off, reinterpret_cast<const uint32_t*>(index), val,
-                                          reinterpret_cast<const uint32_t*>(field), nrows,
-                                          reinterpret_cast<const float*>(v), features, num_fields, k,
-                                          reinterpret_cast<float*>(y),
-                                          reinterpret_cast<int*>(error), stream_of(stream));
-        }
+      [stream_of](const CsrArg& csr, uintptr_t v, uint64_t features, int num_fields, int k,
+                  uintptr_t y, uintptr_t error, uintptr_t stream) {
+        gpu::LaunchFFMForward(View(csr), Ptr<const float>(v), features, num_fields, k,
+                              Ptr<float>(y), Ptr<int>(error), stream_of(stream));
       },
-      py::arg("offset"), py::arg("index"), py::arg("value"), py::arg("field"), py::arg("nrows"),
-      py::arg("v"), py::arg("features"), py::arg("num_fields"), py::arg("k"), py::arg("y"),
-      py::arg("error"), py::arg("stream"), py::arg("index64") = false);
+      py::arg("csr"), py::arg("v"), py::arg("features"), py::arg("num_fields"), py::arg("k"),
+      py::arg("y"), py::arg("error"), py::arg("stream"));
   m.def(
       "ffm_backward",
-      [stream_of](uintptr_t offset, uintptr_t index, uintptr_t value, uintptr_t field, size_t nrows,
-                  uintptr_t g, uintptr_t v, uint64_t features, int num_fields, int k, uintptr_t dv,
-                  uintptr_t stream, bool index64) {
-        auto* off = reinterpret_cast<const uint64_t*>(offset);
-        auto* val = reinterpret_cast<const float*>(value);
-        if (index64) {
-          gpu::LaunchFFMBackward<uint64_t>(off, reinterpret_cast<const uint64_t*>(index), val,
-                                           reinterpret_cast<const uint64_t*>(field), nrows,
-                                           reinterpret_cast<const float*>(g),
-                                           reinterpret_cast<const float*>(v), features, num_fields,
-                                           k, reinterpret_cast<float*>(dv), stream_of(stream));
-        } else {
-          gpu::LaunchFFMBackward<uint32_t>(off, reinterpret_cast<const uint32_t*>(index), val,
-                                           reinterpret_cast<const uint32_t*>(field), nrows,
-                                           reinterpret_cast<const float*>(g),
-                                           reinterpret_cast<const float*>(v), features, num_fields,
-                                           k, reinterpret_cast<float*>(dv), stream_of(stream));
-        }
+      [stream_of](const CsrArg& csr, uintptr_t g, uintptr_t v, uint64_t features, int num_fields,
+                  int k, uintptr_t dv, uintptr_t stream) {
+        gpu::LaunchFFMBackward(View(csr), Ptr<const float>(g), Ptr<const float>(v), features,
+                               num_fields, k, Ptr<float>(dv), stream_of(stream));
       },
-      py::arg("offset"), py::arg("index"), py::arg("value"), py::arg("field"), py::arg("nrows"),
-      py::arg("g"), py::arg("v"), py::arg("features"), py::arg("num_fields"), py::arg("k"),
-      py::arg("dv"), py::arg("stream"), py::arg("index64") = false);
+      py::arg("csr"), py::arg("g"), py::arg("v"), py::arg("features"), py::arg("num_fields"),
+      py::arg("k"), py::arg("dv"), py::arg("stream"));
   m.def("ffm_max_rank", []() { return gpu::kFFMMaxRank; },
         "largest factor rank (a multiple of 4) ops.ffm / ops.ffm_t take");
   m.def("ffm_staged_row_entries", []() { return gpu::kFFMStagedRowEntries; },
         "entries of a row FF1 / FF2 stage in LDS; longer rows re-read global memory");
   m.def(
       "csr_transpose",
-      [stream_of](uintptr_t offset, size_t nrows, uint64_t base, uint64_t nnz, uintptr_t index,
-                  uintptr_t value, uint64_t num_features, uintptr_t col_ptr, uintptr_t row_out,
-                  uintptr_t val_out, uintptr_t scratch, uintptr_t error, uintptr_t stream,
-                  bool index64) {
-        auto* off = reinterpret_cast<const uint64_t*>(offset);
-        auto* val = reinterpret_cast<const float*>(value);
-        auto* cp = reinterpret_cast<uint64_t*>(col_ptr);
-        auto* ro = reinterpret_cast<uint32_t*>(row_out);
-        auto* vo = reinterpret_cast<float*>(val_out);
-        auto* err = reinterpret_cast<uint32_t*>(error);
-        void* sc = reinterpret_cast<void*>(scratch);
-        if (index64) {
-          gpu::LaunchCSRTranspose<uint64_t>(off, nrows, base, nnz,
-                                            reinterpret_cast<const uint64_t*>(index), val,
-                                            num_features, cp, ro, vo, sc, err, stream_of(stream));
-        } else {
-          gpu::LaunchCSRTranspose<uint32_t>(off, nrows, base, nnz,
-                                            reinterpret_cast<const uint32_t*>(index), val,
-                                            num_features, cp, ro, vo, sc, err, stream_of(stream));
-        }
+      [stream_of](const CsrArg& csr, uint64_t base, uint64_t nnz, uint64_t num_features,
+                  uintptr_t col_ptr, uintptr_t row_out, uintptr_t val_out, uintptr_t scratch,
+                  uintptr_t error, uintptr_t stream) {
+        gpu::LaunchCSRTranspose(View(csr), base, nnz, num_features, Ptr<uint64_t>(col_ptr),
+                                Ptr<uint32_t>(row_out), Ptr<float>(val_out), Ptr<void>(scratch),
+                                Ptr<uint32_t>(error), stream_of(stream));
       },
-      py::arg("offset"), py::arg("nrows"), py::arg("base"), py::arg("nnz"), py::arg("index"),
-      py::arg("value"), py::arg("num_features"), py::arg("col_ptr"), py::arg("row_out"),
-      py::arg("val_out"), py::arg("scratch"), py::arg("error"), py::arg("stream"),
-      py::arg("index64") = false);
+      py::arg("csr"), py::arg("base"), py::arg("nnz"), py::arg("num_features"),
+      py::arg("col_ptr"), py::arg("row_out"), py::arg("val_out"), py::arg("scratch"),
+      py::arg("error"), py::arg("stream"));
   m.def("csr_transpose_scratch_bytes", &gpu::CSRTransposeScratchBytes, py::arg("nnz"),
         py::arg("num_features"));
   m.def("csr_transpose_max_features", &gpu::CSRTransposeMaxFeatures);
@@ -1080,16 +995,14 @@ PYBIND11_MODULE(_dmlc, m) {
                   uintptr_t stream) {
         // G1 and the scan of its lengths: out_offset[0 .. n_sel) becomes the
         // batch's row pointer, *total its entry count
-        auto* oo = reinterpret_cast<uint64_t*>(out_offset);
-        gpu::LaunchCSRGatherCount(
-            reinterpret_cast<const uint64_t*>(offset), nrows_src, src_entries,
-            reinterpret_cast<const void*>(rows), rows64, n_sel,
-            reinterpret_cast<const float*>(label), reinterpret_cast<const float*>(weight),
-            reinterpret_cast<const uint64_t*>(qid), oo, reinterpret_cast<float*>(out_label),
-            reinterpret_cast<float*>(out_weight), reinterpret_cast<uint64_t*>(out_qid),
-            reinterpret_cast<uint32_t*>(error), stream_of(stream));
-        gpu::LaunchScanU64(oo, n_sel, reinterpret_cast<uint64_t*>(scratch),
-                           reinterpret_cast<uint64_t*>(total), stream_of(stream));
+        auto* oo = Ptr<uint64_t>(out_offset);
+        gpu::LaunchCSRGatherCount(Ptr<const uint64_t>(offset), nrows_src, src_entries,
+                                  Ptr<const void>(rows), rows64, n_sel, Ptr<const float>(label),
+                                  Ptr<const float>(weight), Ptr<const uint64_t>(qid), oo,
+                                  Ptr<float>(out_label), Ptr<float>(out_weight),
+                                  Ptr<uint64_t>(out_qid), Ptr<uint32_t>(error), stream_of(stream));
+        gpu::LaunchScanU64(oo, n_sel, Ptr<uint64_t>(scratch), Ptr<uint64_t>(total),
+                           stream_of(stream));
       },
       py::arg("offset"), py::arg("nrows_src"), py::arg("src_entries"), py::arg("rows"),
       py::arg("rows64"), py::arg("n_sel"), py::arg("label"), py::arg("weight"), py::arg("qid"),
@@ -1097,72 +1010,35 @@ PYBIND11_MODULE(_dmlc, m) {
       py::arg("scratch"), py::arg("total"), py::arg("error"), py::arg("stream"));
   m.def(
       "csr_gather_fill",
-      [stream_of](uintptr_t offset, uint64_t nrows_src, uint64_t src_entries, uintptr_t rows,
-                  bool rows64, size_t n_sel, uintptr_t out_offset, uintptr_t total,
-                  uintptr_t index, uintptr_t value, uintptr_t field, uintptr_t out_index,
-                  uintptr_t out_value, uintptr_t out_field,
-                  uint64_t out_capacity, uintptr_t error, uintptr_t stream, bool index64) {
-        auto* off = reinterpret_cast<const uint64_t*>(offset);
-        auto* rw = reinterpret_cast<const void*>(rows);
-        auto* oo = reinterpret_cast<uint64_t*>(out_offset);
-        auto* tot = reinterpret_cast<const uint64_t*>(total);
-        auto* val = reinterpret_cast<const float*>(value);
-        auto* oval = reinterpret_cast<float*>(out_value);
-        auto* err = reinterpret_cast<uint32_t*>(error);
-        if (index64) {
-          gpu::LaunchCSRGatherFill<uint64_t>(
-              off, nrows_src, src_entries, rw, rows64, n_sel, oo, tot,
-              reinterpret_cast<const uint64_t*>(index), val,
-              reinterpret_cast<const uint64_t*>(field), reinterpret_cast<uint64_t*>(out_index), oval,
-              reinterpret_cast<uint64_t*>(out_field), out_capacity, err, stream_of(stream));
-        } else {
-          gpu::LaunchCSRGatherFill<uint32_t>(
-              off, nrows_src, src_entries, rw, rows64, n_sel, oo, tot,
-              reinterpret_cast<const uint32_t*>(index), val,
-              reinterpret_cast<const uint32_t*>(field), reinterpret_cast<uint32_t*>(out_index), oval,
-              reinterpret_cast<uint32_t*>(out_field), out_capacity, err, stream_of(stream));
-        }
+      [stream_of](const CsrArg& csr, uint64_t src_entries, uintptr_t rows, bool rows64,
+                  size_t n_sel, uintptr_t out_offset, uintptr_t total, uintptr_t out_index,
+                  uintptr_t out_value, uintptr_t out_field, uint64_t out_capacity,
+                  uintptr_t error, uintptr_t stream) {
+        gpu::LaunchCSRGatherFill(View(csr), src_entries, Ptr<const void>(rows), rows64, n_sel,
+                                 Ptr<uint64_t>(out_offset), Ptr<const uint64_t>(total),
+                                 Ptr<void>(out_index), Ptr<float>(out_value), Ptr<void>(out_field),
+                                 out_capacity, Ptr<uint32_t>(error), stream_of(stream));
       },
-      py::arg("offset"), py::arg("nrows_src"), py::arg("src_entries"), py::arg("rows"),
-      py::arg("rows64"), py::arg("n_sel"), py::arg("out_offset"), py::arg("total"), py::arg("index"),
-      py::arg("value"), py::arg("field"), py::arg("out_index"), py::arg("out_value"),
-      py::arg("out_field"), py::arg("out_capacity"), py::arg("error"), py::arg("stream"),
-      py::arg("index64") = false);
+      py::arg("csr"), py::arg("src_entries"), py::arg("rows"), py::arg("rows64"),
+      py::arg("n_sel"), py::arg("out_offset"), py::arg("total"), py::arg("out_index"),
+      py::arg("out_value"), py::arg("out_field"), py::arg("out_capacity"), py::arg("error"),
+      py::arg("stream"));
   m.def("csr_gather_scratch_words", &gpu::CSRGatherScratchWords, py::arg("n_sel"));
   m.def("csr_gather_run_entries", &gpu::CSRGatherRunEntries);
   m.def(
       "hashed_dense",
-      [stream_of](uintptr_t offset, uintptr_t index, uintptr_t value, uintptr_t field,
-                  size_t nrows, int dim, float scale, uint32_t seed, uintptr_t out, bool fp8,
-                  uintptr_t stream, bool index64) {
+      [stream_of](const CsrArg& csr, int dim, float scale, uint32_t seed, uintptr_t out, bool fp8,
+                  uintptr_t stream) {
         CHECK(dim > 0 && dim <= 8192 && dim % 4 == 0) << "dim must be a multiple of 4 in (0, 8192]";
-        auto* off = reinterpret_cast<const uint64_t*>(offset);
-        auto* val = reinterpret_cast<const float*>(value);
-        if (index64) {
-          auto* idx = reinterpret_cast<const uint64_t*>(index);
-          auto* fld = reinterpret_cast<const uint64_t*>(field);
-          if (fp8) {
-            gpu::LaunchHashedDenseFP8<uint64_t>(off, idx, val, fld, nrows, dim, scale, seed,
-                                                reinterpret_cast<uint8_t*>(out), stream_of(stream));
-          } else {
-            gpu::LaunchHashedDenseF32<uint64_t>(off, idx, val, fld, nrows, dim, seed,
-                                                reinterpret_cast<float*>(out), stream_of(stream));
-          }
+        if (fp8) {
+          gpu::LaunchHashedDenseFP8(View(csr), dim, scale, seed, Ptr<uint8_t>(out),
+                                    stream_of(stream));
         } else {
-          auto* idx = reinterpret_cast<const uint32_t*>(index);
-          auto* fld = reinterpret_cast<const uint32_t*>(field);
-          if (fp8) {
-            gpu::LaunchHashedDenseFP8<uint32_t>(off, idx, val, fld, nrows, dim, scale, seed,
-                                                reinterpret_cast<uint8_t*>(out), stream_of(stream));
-          } else {
-            gpu::LaunchHashedDenseF32<uint32_t>(off, idx, val, fld, nrows, dim, seed,
-                                                reinterpret_cast<float*>(out), stream_of(stream));
-          }
+          gpu::LaunchHashedDenseF32(View(csr), dim, seed, Ptr<float>(out), stream_of(stream));
         }
       },
-      py::arg("offset"), py::arg("index"), py::arg("value"), py::arg("field"), py::arg("nrows"),
-      py::arg("dim"), py::arg("scale"), py::arg("seed"), py::arg("out"), py::arg("fp8"),
-      py::arg("stream"), py::arg("index64") = false);
+      py::arg("csr"), py::arg("dim"), py::arg("scale"), py::arg("seed"), py::arg("out"),
+      py::arg("fp8"), py::arg("stream"));
   m.def(
       "read_partition",
       [](const std::string& uri, unsigned part, unsigned nparts, const std::string& type,

@@ -481,6 +481,33 @@ def test_k11_pairs_over_a_transpose(many_rows):
     _close(ops.spmv(small, torch.from_numpy(d).cuda(), 0.0), g[:1000], gtol[:1000])
 
 
+def test_pairs_and_unpaired_agree():
+    """a transpose read as interleaved pairs (k_spmv_pairs, M1p) and as its
+    contiguous copies (k_spmv, M1): K11 sums in no fixed order, so the two
+    agree within its any-order bound; M1 and M1p promise one summation order,
+    so the SpMM bytes are equal"""
+    rng = np.random.default_rng(133)
+    nrows, nfeat = 133, 257
+    lens = np.resize([0, 1, 15, 16, 17, 70], nrows)
+    off, idx, val, t = _spmv_case(False, True, rng, lens=lens, nfeat=nfeat)
+    tt = ops.transpose(t, nfeat)
+    flat = ops._unpair(tt)
+    assert ops._paired(tt) and not ops._paired(flat)
+    assert flat["index"].is_contiguous() and flat["value"].is_contiguous()
+    d = rng.standard_normal(nrows).astype(np.float32)
+    g, gtol = pyref.csr_dot_t_ref(off, idx, val, d, nfeat)
+    dd = torch.from_numpy(d).cuda()
+    paired, unpaired = ops.spmv(tt, dd), ops.spmv(flat, dd)
+    _close(paired, g, gtol)
+    _close(unpaired, g, gtol)
+    _close(paired, unpaired.cpu().numpy().astype(np.float64), gtol)
+    for k in (1, 4, 7):
+        D = torch.from_numpy(rng.standard_normal((nrows, k)).astype(np.float32)).cuda()
+        a, b = ops.spmm(tt, D), ops.spmm(flat, D)
+        assert a.shape == (nfeat, k)
+        assert torch.equal(a.view(torch.int32), b.view(torch.int32)), k
+
+
 # ------------------------------------------------------------------ parser
 def test_exact_path_scans_more_than_one_partial(tmp_path):
     """20 000 short lines in one chunk on the exact per-line path: its offsets
