@@ -11,9 +11,11 @@ from typing import Optional
 
 import torch
 
-from ..ops import _stream, csr_ffm, csr_spmm, csr_spmv, hashed_dense
+from ..ops import (_stream, csr_ffm, csr_spmm, csr_spmv, hashed_dense, ndcg, qid_groups,
+                   rank_loss)
 
-__all__ = ["SparseLogReg", "HashedFM", "SparseSoftmaxReg", "SparseFM", "SparseFFM"]
+__all__ = ["SparseLogReg", "HashedFM", "SparseSoftmaxReg", "SparseFM", "SparseFFM",
+           "SparseRanker"]
 
 
 class SparseLogReg(torch.nn.Module):
@@ -222,6 +224,129 @@ class SparseFFM(torch.nn.Module):
             term = x[a] * x[c] * (v[idx[a], fld[c]] * v[idx[c], fld[a]]).sum(-1)
             y = y + torch.zeros(rows, dtype=w.dtype).index_add(0, owner, term)
         return y
+
+
+def _group_ptr(csr) -> torch.Tensor:
+    """``csr["group_ptr"]`` if the dict has one; else the pointer of
+    ``csr["qid"]``'s runs, made once per qid tensor and cached in the dict
+    (keyed as :func:`_squared_values` keys its cache)"""
+    ptr = csr.get("group_ptr")
+    if ptr is not None:
+        return ptr
+    qid = csr.get("qid")
+    if not isinstance(qid, torch.Tensor):
+        raise ValueError("SparseRanker: csr has neither 'group_ptr' nor a 'qid' tensor "
+                         "(parse a LibSVM file with qid: tokens)")
+    key = (int(qid.data_ptr()), qid.numel(), qid._version)
+    cached = csr.get("_group_ptr")
+    if cached is None or cached[0] != key:
+        if qid.is_cuda:
+            ptr = qid_groups(qid)
+        else:
+            q = qid.view(torch.int64) if qid.dtype == torch.uint64 else qid
+            start = torch.ones(q.numel(), dtype=torch.bool)
+            start[1:] = q[1:] != q[:-1]
+            ptr = torch.cat([torch.nonzero(start).reshape(-1),
+                             torch.tensor([q.numel()])]).to(torch.int64)
+        cached = (key, ptr)
+        csr["_group_ptr"] = cached
+    return cached[1]
+
+
+class SparseRanker(torch.nn.Module):
+    """Linear learning to rank on the query groups of a LibSVM file with
+    ``qid:`` tokens: score = x . w, trained with the pairwise loss of
+    :func:`~dmlc_core_amd.ops.rank_loss` -- RankNet (``weighting="none"``) or
+    LambdaRank (``"ndcg"``) -- over the pairs of every group.  There is no
+    trainable bias: a bias cancels in every pair.  Labels are integer
+    relevance grades in [0, 31]; row weights (``csr["weight"]``) are not used.
+    On the device the score is :func:`~dmlc_core_amd.ops.csr_spmv` (``grad``
+    as there) and the loss the HIP kernels RK1 / RK2; on host tensors
+    :meth:`reference` evaluates the definitions with torch ops."""
+
+    def __init__(self, num_features: int, grad: str = "auto"):
+        super().__init__()
+        self.num_features = int(num_features)
+        self.grad = grad  # X^T g: "auto" / "transpose" (cached inverted index) / "atomic"
+        self.weight = torch.nn.Parameter(torch.zeros(self.num_features, dtype=torch.float32))
+
+    def forward(self, csr) -> torch.Tensor:
+        if not csr["index"].is_cuda:
+            return _dense(csr, self.num_features) @ self.weight
+        zero = torch.zeros(1, dtype=torch.float32, device=self.weight.device)
+        return csr_spmv(csr, self.weight, zero, grad=self.grad)
+
+    def loss(self, csr, weighting: str = "ndcg", sigma: float = 1.0,
+             validate: bool = True) -> torch.Tensor:
+        """Mean over the groups that have a pair of the pairwise loss against
+        ``csr["label"]``.  The groups are ``csr["group_ptr"]`` if present, else
+        the runs of ``csr["qid"]`` (:func:`~dmlc_core_amd.ops.qid_groups`,
+        cached in the dict)."""
+        ptr = _group_ptr(csr)
+        score = self.forward(csr)
+        if not score.is_cuda:
+            return self.reference(score, csr["label"], ptr, weighting, sigma)
+        return rank_loss(score, csr["label"], ptr, weighting, sigma, validate)
+
+    @torch.no_grad()
+    def ndcg(self, csr, k: Optional[int] = 10) -> torch.Tensor:
+        """Mean NDCG@k over the groups (a group without a relevant row counts 1.0)"""
+        ptr = _group_ptr(csr)
+        score = self.forward(csr)
+        if not score.is_cuda:
+            return self.reference_ndcg(score, csr["label"], ptr, k).mean()
+        return ndcg(score, csr["label"], ptr, k).mean()
+
+    @staticmethod
+    def _ranks(key: torch.Tensor) -> torch.Tensor:
+        """0-based positions in a stable descending sort of ``key``"""
+        order = torch.sort(key, descending=True, stable=True).indices
+        pos = torch.empty_like(order)
+        pos[order] = torch.arange(order.numel())
+        return pos
+
+    @staticmethod
+    def reference(score, label, group_ptr, weighting: str = "ndcg", sigma: float = 1.0):
+        """The loss's definition (:func:`~dmlc_core_amd.ops.rank_loss_parts`)
+        on host tensors, with torch ops in the dtype of ``score``,
+        differentiable in ``score``: every group's pairs as an [n, n] mask."""
+        if weighting not in ("ndcg", "none"):
+            raise ValueError(f"weighting must be 'ndcg' or 'none', got {weighting!r}")
+        dt = score.dtype
+        total, counted = torch.zeros((), dtype=dt), 0
+        for b, e in zip(group_ptr[:-1].tolist(), group_ptr[1:].tolist()):
+            s, lab = score[b:e], label[b:e].to(dt)
+            pair = lab[:, None] > lab[None, :]
+            npairs = int(pair.sum())
+            if npairs == 0:
+                continue
+            x = sigma * (s[:, None] - s[None, :])
+            term = torch.nn.functional.softplus(-x)
+            if weighting == "ndcg":
+                gain = torch.exp2(lab) - 1
+                disc = 1 / torch.log2(2 + SparseRanker._ranks(s.detach()).to(dt))
+                ideal = (gain / torch.log2(2 + SparseRanker._ranks(lab).to(dt))).sum()
+                term = term * ((gain[:, None] - gain[None, :]).abs()
+                               * (disc[:, None] - disc[None, :]).abs() / ideal)
+            total = total + (term * pair).sum() / npairs
+            counted += 1
+        return total / max(1, counted)
+
+    @staticmethod
+    def reference_ndcg(score, label, group_ptr, k: Optional[int] = None) -> torch.Tensor:
+        """NDCG@k of every group on host tensors (:func:`~dmlc_core_amd.ops.ndcg`),
+        in the dtype of ``score``"""
+        dt = score.dtype
+        out = []
+        for b, e in zip(group_ptr[:-1].tolist(), group_ptr[1:].tolist()):
+            s, lab = score[b:e].detach(), label[b:e].to(dt)
+            kk = e - b if k is None else k
+            gain = torch.exp2(lab) - 1
+            r, q = SparseRanker._ranks(s), SparseRanker._ranks(lab)
+            dcg = (gain / torch.log2(2 + r.to(dt)))[r < kk].sum()
+            ideal = (gain / torch.log2(2 + q.to(dt)))[q < kk].sum()
+            out.append(dcg / ideal if float(ideal) > 0 else torch.ones((), dtype=dt))
+        return torch.stack(out) if out else torch.zeros(0, dtype=dt)
 
 
 class _HashedFMFunction(torch.autograd.Function):

@@ -2,8 +2,9 @@
 
 Every op launches a hand-written CDNA4 kernel from ``libdmlc.so`` on the
 current torch stream (src/gpu/feature_kernels.hip, spmm_kernels.hip,
-transpose_kernels.hip, gather_kernels.hip, ffm_kernels.hip).  There is no PyTorch
-fallback: on a machine without the extension or a GPU these functions raise.
+transpose_kernels.hip, gather_kernels.hip, ffm_kernels.hip, rank_kernels.hip).
+There is no PyTorch fallback: on a machine without the extension or a GPU these
+functions raise.
 
 CSR arguments are the dict returned by :func:`dmlc_core_amd.data.csr_to_torch`
 (``offset`` int64/uint64 [rows+1], ``index`` int32/uint32 or 64-bit [nnz],
@@ -20,7 +21,8 @@ from .. import _dmlc
 __all__ = ["spmv", "spmv_t", "hashed_dense", "SpMVFunction", "csr_spmv", "transpose",
            "gather_rows", "gather_buffers", "release_workspace",
            "spmm", "spmm_t", "SpMMFunction", "csr_spmm",
-           "ffm", "ffm_t", "FFMFunction", "csr_ffm"]
+           "ffm", "ffm_t", "FFMFunction", "csr_ffm",
+           "qid_groups", "group_rows", "rank_loss", "rank_loss_parts", "RankLossFunction", "ndcg"]
 
 # persistent transpose scratch per (device, stream), grow-only: a rebuild (a
 # further shard, a refreshed batch) allocates no multi-GB scratch again
@@ -718,6 +720,225 @@ def csr_ffm(csr: Dict, v: torch.Tensor, validate: bool = True) -> torch.Tensor:
     back."""
     return FFMFunction.apply(v, (csr["offset"], csr["index"], csr.get("value"), csr.get("field")),
                              validate)
+
+
+_RANK_ERR_GROUP, _RANK_ERR_LABEL = 1, 2  # kRankErr* (src/gpu/kernels.h)
+_RANK_WEIGHTINGS = ("ndcg", "none")
+
+
+def qid_groups(qid: torch.Tensor) -> torch.Tensor:
+    """The group pointer of a ``qid`` column (Q1 / Q2, src/gpu/rank_kernels.hip):
+    int64 ``[G + 1]`` with group g = rows ``[ptr[g], ptr[g + 1])``, one group per
+    run of equal ids.  Rows of one query are taken to be adjacent, as ranking
+    files are written: a qid that comes back after another starts a new group.
+
+    ``qid``: a 1-D contiguous 64-bit device tensor (``csr_to_torch``'s int64 or
+    a uint64 one; ids are only compared for equality, so values from 2^63 up
+    are ids like any other); anything else raises ``ValueError``.  Q1 flags the
+    run starts, the K3 scan numbers them, Q2 writes each start's row.  Exactly
+    one device-to-host read, of G, between the scan and Q2 (it sizes the
+    result); the flags live in the persistent workspace of :func:`transpose`.
+    Empty input gives ``tensor([0])`` without a launch."""
+    if not isinstance(qid, torch.Tensor) or qid.dim() != 1:
+        raise ValueError("qid must be a 1-D tensor")
+    if qid.dtype not in (torch.int64, torch.uint64):
+        raise ValueError(f"qid must be a 64-bit integer tensor, got {qid.dtype}")
+    if not qid.is_cuda or not qid.is_contiguous():
+        raise ValueError("qid must be a contiguous device tensor")
+    rows, dev = qid.numel(), qid.device
+    if rows == 0:
+        return torch.zeros(1, dtype=torch.int64, device=dev)
+    words = rows + int(_dmlc.qid_scan_words(rows)) + 1
+    ws = _workspace(8 * words + 16, dev)
+    flag = (_ptr(ws) + 15) // 16 * 16  # the scan's 16-byte loads
+    partials, total = flag + 8 * rows, flag + 8 * (words - 1)
+    stream = _stream()
+    _dmlc.qid_flags(_ptr(qid), rows, flag, partials, total, stream)
+    tot = ws[total - _ptr(ws):total - _ptr(ws) + 8].view(torch.int64)
+    groups = int(tot.item())
+    ptr = torch.empty(groups + 1, dtype=torch.int64, device=dev)
+    _dmlc.qid_group_ptr(_ptr(qid), rows, flag, total, groups, _ptr(ptr), stream)
+    return ptr
+
+
+def group_rows(group_ptr: torch.Tensor, groups: torch.Tensor):
+    """The row ids of the groups ``groups[0], groups[1], ...`` of a group
+    pointer, in that order, and their own pointer: ``(rows int64 [n], batch_ptr
+    int64 [len(groups) + 1])`` on ``group_ptr``'s device.  With
+    :func:`gather_rows` this gathers whole queries -- a group-shuffled
+    minibatch whose ``batch_ptr`` is the batch's ``group_ptr``.  torch ops only
+    (one read, of n, inside ``repeat_interleave``); group ids must be in
+    ``[0, G)``, which is not checked."""
+    if not isinstance(group_ptr, torch.Tensor) or group_ptr.dim() != 1 or group_ptr.numel() < 1 \
+            or group_ptr.dtype != torch.int64:
+        raise ValueError("group_ptr must be a 1-D int64 tensor [G + 1]")
+    if not isinstance(groups, torch.Tensor) or groups.dim() != 1 \
+            or groups.dtype not in (torch.int64, torch.int32):
+        raise ValueError("groups must be a 1-D int64 or int32 tensor of group ids")
+    sel = groups.to(device=group_ptr.device, dtype=torch.int64)
+    start = group_ptr[sel]
+    lens = group_ptr[sel + 1] - start
+    batch_ptr = torch.zeros(sel.numel() + 1, dtype=torch.int64, device=group_ptr.device)
+    torch.cumsum(lens, 0, out=batch_ptr[1:])
+    # row p of the batch belongs to selected group o: start[o] + (p - batch_ptr[o])
+    owner = torch.repeat_interleave(torch.arange(sel.numel(), device=group_ptr.device), lens)
+    rows = torch.arange(owner.numel(), device=group_ptr.device) - batch_ptr[owner] + start[owner]
+    return rows, batch_ptr
+
+
+def _check_rank(name: str, score, label, group_ptr) -> tuple:
+    """the operands of :func:`rank_loss` / :func:`ndcg`, before anything is
+    launched; returns (rows, groups)"""
+    for what, t in (("score", score), ("label", label)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 1:
+            raise ValueError(f"{name}: {what} must be a 1-D tensor [rows]")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name}: {what} must be float32, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: {what} must be contiguous")
+    if not isinstance(group_ptr, torch.Tensor) or group_ptr.dim() != 1 or group_ptr.numel() < 1:
+        raise ValueError(f"{name}: group_ptr must be a 1-D tensor [G + 1]")
+    if group_ptr.dtype != torch.int64:
+        raise ValueError(f"{name}: group_ptr must be int64, got {group_ptr.dtype}")
+    if not group_ptr.is_contiguous():
+        raise ValueError(f"{name}: group_ptr must be contiguous")
+    if label.numel() != score.numel():
+        raise ValueError(f"{name}: label has {label.numel()} entries, score {score.numel()}")
+    for what, t in (("score", score), ("label", label), ("group_ptr", group_ptr)):
+        if not t.is_cuda:
+            raise ValueError(f"{name}: {what} must be a device tensor")
+        if t.device != score.device:
+            raise ValueError(f"{name}: {what} must be on score's device ({score.device}), "
+                             f"is on {t.device}")
+    return score.numel(), group_ptr.numel() - 1
+
+
+def _check_rank_loss(score, label, group_ptr, weighting, sigma) -> tuple:
+    """the two settings of the loss, then :func:`_check_rank`"""
+    if weighting not in _RANK_WEIGHTINGS:
+        raise ValueError(f"rank_loss: weighting must be one of {_RANK_WEIGHTINGS}, got {weighting!r}")
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, float)) or not sigma > 0:
+        raise ValueError(f"rank_loss: sigma must be a number > 0, got {sigma!r}")
+    return _check_rank("rank_loss", score, label, group_ptr)
+
+
+def _raise_rank_errors(name: str, err: torch.Tensor, rows: int) -> None:
+    """the one read of a validated call: the kernels' error word"""
+    bits = int(err.item())
+    if bits:
+        what = [s for b, s in ((_RANK_ERR_GROUP, f"group_ptr descends or points past the rows ({rows}), "
+                                                 "or a group spans 2^31 rows"),
+                               (_RANK_ERR_LABEL, "a label is not an integer in "
+                                                 f"[0, {int(_dmlc.rank_max_label())}]"))
+                if bits & b]
+        raise ValueError(f"{name}: " + " and ".join(what))
+
+
+def rank_loss_parts(score: torch.Tensor, label: torch.Tensor, group_ptr: torch.Tensor,
+                    weighting: str = "ndcg", sigma: float = 1.0, validate: bool = True):
+    """The pairwise ranking loss of every query group and its gradient (RK1 /
+    RK2, src/gpu/rank_kernels.hip), without autograd: ``(loss_g float32 [G],
+    pairs_g int64 [G], grad float32 [rows])``.
+
+    Group g is rows ``[group_ptr[g], group_ptr[g + 1])``, of any length from 0.
+    Row i has score ``s_i``, label ``l_i`` (a float32 holding an integer in
+    ``[0, _dmlc.rank_max_label()]`` = 31) and gain ``G_i = 2^l_i - 1``; ``r_i``
+    is its 0-based position in a stable descending sort of the group by score,
+    ``q_i`` by label, ``D(r) = 1 / log2(2 + r)`` and ``IDCG = sum_i G_i D(q_i)``.
+    Over the pairs ``P = {(i, j) : l_i > l_j}`` with ``x_ij = sigma (s_i - s_j)``
+
+        loss_g  = 1/|P| sum_P w_ij softplus(-x_ij)             (0 without pairs)
+        grad[i] = sigma/|P| (- sum_{j: l_i > l_j} w_ij rho(x_ij)
+                             + sum_{j: l_j > l_i} w_ji rho(x_ji)),  rho(z) = 1 / (1 + e^z)
+
+    where ``weighting="none"`` (RankNet) has ``w_ij = 1`` and ``"ndcg"``
+    (LambdaRank) ``w_ij = |G_i - G_j| |D(r_i) - D(r_j)| / IDCG``, treated as a
+    constant: it is piecewise constant in s, so ``grad`` is d loss_g / d s_i
+    almost everywhere.  ``pairs_g`` is ``|P|``.  Rows outside every group get
+    gradient 0.  Row weights (``csr["weight"]``) are not used.
+
+    One wave takes a group of up to ``_dmlc.rank_wave_group_rows()`` (256) rows
+    staged in LDS, one workgroup a longer one (below 2^31 rows) in tiles; both
+    kernels are launched once over all groups and no length is read back.  No
+    sort and no atomics: ranks are counted, every row's sum has one owner, and
+    the same inputs give the same bytes.  With ``"ndcg"`` a float per row of
+    scratch comes from the persistent workspace of :func:`transpose`.
+
+    ``score`` / ``label``: contiguous float32 device tensors ``[rows]``;
+    ``group_ptr``: a contiguous int64 device tensor ``[G + 1]`` (it may start
+    above 0 and end below ``rows``); ``sigma > 0``.  Anything else raises
+    ``ValueError`` before a launch.  A group whose pointers descend or end past
+    ``rows``, and a group with a label that is negative, fractional, NaN or
+    above 31, forms no address and no pair: its loss and pairs are 0, its rows'
+    gradient 0, and it is flagged.  ``validate=True`` reads the flag word --
+    the one device-to-host read of the call -- and raises ``ValueError`` naming
+    the check; ``validate=False`` reads nothing.  NaN scores violate a
+    precondition: their group's outputs are unspecified."""
+    rows, groups = _check_rank_loss(score, label, group_ptr, weighting, sigma)
+    dev = score.device
+    grad = torch.zeros(rows, dtype=torch.float32, device=dev)
+    loss_g = torch.zeros(groups, dtype=torch.float32, device=dev)
+    pairs_g = torch.zeros(groups, dtype=torch.int64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    weighted = weighting == "ndcg"
+    scratch = _workspace(4 * rows, dev) if weighted else None
+    _dmlc.rank_loss(_ptr(score), _ptr(label), _ptr(group_ptr), groups, rows, weighted, float(sigma),
+                    _ptr(scratch), _ptr(grad), _ptr(loss_g), _ptr(pairs_g), _ptr(err), _stream())
+    if validate:
+        _raise_rank_errors("rank_loss", err, rows)
+    return loss_g, pairs_g, grad
+
+
+class RankLossFunction(torch.autograd.Function):
+    """Autograd wrapper of :func:`rank_loss_parts`: the forward launches RK1 and
+    RK2 once and keeps the gradient; the backward scales it by the incoming
+    gradient and by 1 / max(1, groups with pairs), which stays on the device."""
+
+    @staticmethod
+    def forward(ctx, score, label, group_ptr, weighting, sigma, validate):
+        loss_g, pairs_g, grad = rank_loss_parts(score.detach(), label, group_ptr, weighting, sigma,
+                                                validate)
+        inv = 1.0 / (pairs_g > 0).sum().clamp(min=1).to(torch.float32)
+        ctx.save_for_backward(grad, inv)
+        return loss_g.sum() * inv
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        grad, inv = ctx.saved_tensors
+        return grad * (grad_out * inv), None, None, None, None, None
+
+
+def rank_loss(score: torch.Tensor, label: torch.Tensor, group_ptr: torch.Tensor,
+              weighting: str = "ndcg", sigma: float = 1.0, validate: bool = True) -> torch.Tensor:
+    """Differentiable mean pairwise ranking loss, ``sum_g loss_g / max(1, #{g :
+    |P_g| > 0})``: :func:`rank_loss_parts` (its arguments, checks and
+    definitions; row weights are not used) behind :class:`RankLossFunction`,
+    differentiable in ``score``."""
+    _check_rank_loss(score, label, group_ptr, weighting, sigma)
+    return RankLossFunction.apply(score, label, group_ptr, weighting, sigma, validate)
+
+
+def ndcg(score: torch.Tensor, label: torch.Tensor, group_ptr: torch.Tensor,
+         k: Optional[int] = None, validate: bool = True) -> torch.Tensor:
+    """NDCG@k of every query group, float32 ``[G]`` (RK1 / RK2 in metric mode:
+    the rank counting of :func:`rank_loss_parts`, whose definitions and operand
+    checks apply): ``sum_{i: r_i < k} G_i D(r_i) / sum_{i: q_i < k} G_i D(q_i)``;
+    ``k=None`` is the whole group, and a group whose denominator is 0 (no rows,
+    or only label 0) gives 1.0.  Ties in the scores are ranked by row position.
+    Row weights are not used.  ``k``: None or an integer >= 1.  ``validate`` as
+    for :func:`rank_loss_parts`; a refused group gives 0."""
+    if k is not None and (isinstance(k, bool) or not isinstance(k, int) or k < 1):
+        raise ValueError(f"ndcg: k must be None or an integer >= 1, got {k!r}")
+    rows, groups = _check_rank("ndcg", score, label, group_ptr)
+    cut = 0xFFFFFFFF if k is None else min(int(k), 0xFFFFFFFF)
+    dev = score.device
+    out = torch.zeros(groups, dtype=torch.float32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    _dmlc.rank_ndcg(_ptr(score), _ptr(label), _ptr(group_ptr), groups, rows, cut, _ptr(out),
+                    _ptr(err), _stream())
+    if validate:
+        _raise_rank_errors("ndcg", err, rows)
+    return out
 
 
 def csr_spmv(csr: Dict, w: torch.Tensor, bias: torch.Tensor, grad: str = "auto") -> torch.Tensor:

@@ -19,6 +19,10 @@
  *   M2 spmm transposed   LaunchCSRSpMMT           (spmm_kernels.hip)
  *   FF1 ffm forward      LaunchFFMForward         (ffm_kernels.hip)
  *   FF2 ffm backward     LaunchFFMBackward        (ffm_kernels.hip)
+ *   Q1 qid run flags     LaunchQidFlags           (rank_kernels.hip)
+ *   Q2 qid group pointer LaunchQidGroupPtr        (rank_kernels.hip)
+ *   RK1 rank, wave/group LaunchRankLoss, LaunchRankNdcg (rank_kernels.hip)
+ *   RK2 rank, block/group the same launchers, groups above kRankWaveGroupRows
  *   G1 row gather count  LaunchCSRGatherCount     (gather_kernels.hip)
  *   G2 row gather fill   LaunchCSRGatherFill      (gather_kernels.hip)
  *   CSR -> CSC           LaunchCSRTranspose       (transpose_kernels.hip)
@@ -471,6 +475,55 @@ void LaunchFFMForward(const CsrView& csr, const float* v, uint64_t features, int
  */
 void LaunchFFMBackward(const CsrView& csr, const float* g, const float* v, uint64_t features,
                        int num_fields, int k, float* dv, hipStream_t stream);
+// --------------------- ranking on qid groups (rank_kernels.hip) ---------------------
+/*! \brief largest label of RK1 / RK2 (labels are integers from 0; gain 2^label - 1) */
+constexpr uint32_t kRankMaxLabel = 31;
+/*! \brief rows of a group RK1 takes (one wave, the group staged in LDS); longer groups are RK2's */
+constexpr uint32_t kRankWaveGroupRows = 256;
+/*! \brief rows of the tiles RK2 passes a group through LDS in */
+constexpr uint32_t kRankTileRows = 256;
+/*! \brief bits RK1 / RK2 OR into their error word: a group whose pointers descend, end past
+ *  `rows` or span >= 2^31 rows; a label that is no integer in [0, kRankMaxLabel] */
+constexpr uint32_t kRankErrGroup = 1, kRankErrLabel = 2;
+/*!
+ * \brief Q1: flag[r] = (r == 0 || qid[r] != qid[r - 1]) for r < rows, as u64 for
+ *  LaunchScanU64 (flag 16-byte aligned): scanned, flag[r] is the group of a row
+ *  that starts a run and the scan's total the number of groups G.  Rows of one
+ *  query are taken to be adjacent; a qid that comes back later starts a new group.
+ */
+void LaunchQidFlags(const uint64_t* qid, size_t rows, uint64_t* flag, hipStream_t stream);
+/*!
+ * \brief Q2: group_ptr[scanned[r]] = r at every run start and group_ptr[*total]
+ *  = rows; scanned / total: Q1's flags after LaunchScanU64.  group_ptr has
+ *  capacity + 1 slots (capacity >= *total); a slot past them is not written.
+ */
+void LaunchQidGroupPtr(const uint64_t* qid, size_t rows, const uint64_t* scanned,
+                       const uint64_t* total, uint64_t capacity, uint64_t* group_ptr,
+                       hipStream_t stream);
+/*!
+ * \brief RK1 + RK2: the pairwise ranking loss of every group g = rows
+ *  [group_ptr[g], group_ptr[g + 1]) of score / label [rows] and its gradient
+ *  (the definitions: rank_kernels.hip).  ndcg_weights: LambdaRank's w_ij, else
+ *  1 (RankNet).  Writes loss_g [groups], pairs_g [groups] (|P_g|) and grad[r]
+ *  for the rows of every group that has no error; grad [rows] must be zeroed by
+ *  the caller (rows outside every group and rows of a refused group keep 0).
+ *  row_scratch: `rows` floats (only read and written with ndcg_weights; may be
+ *  null without).  error: an int32 the caller zeroed, kRankErr* bits.  NaN
+ *  scores violate a precondition (the outputs of their group are unspecified;
+ *  no address depends on a score).  Both kernels run over all groups and each
+ *  skips the other's; no atomics on the outputs, the same inputs give the same
+ *  bytes.  groups == 0 returns before any HIP call.
+ */
+void LaunchRankLoss(const float* score, const float* label, const uint64_t* group_ptr, size_t groups,
+                    uint64_t rows, bool ndcg_weights, float sigma, float* row_scratch, float* grad,
+                    float* loss_g, int64_t* pairs_g, int* error, hipStream_t stream);
+/*!
+ * \brief RK1 + RK2 in metric mode: ndcg[g] = NDCG@k of group g (k >= 1; k >=
+ *  the group's length is the whole group; a group whose ideal DCG is 0 gives
+ *  1).  The same rank counting as LaunchRankLoss; a refused group gives 0.
+ */
+void LaunchRankNdcg(const float* score, const float* label, const uint64_t* group_ptr, size_t groups,
+                    uint64_t rows, uint32_t k, float* ndcg, int* error, hipStream_t stream);
 // ------------------------ HashedFM (fm_kernels.hip) ------------------------
 /*! \brief factor rank of the HIP HashedFM kernels and the [w | V] column count */
 constexpr int kFmRank = 16;

@@ -972,6 +972,63 @@ PYBIND11_MODULE(_dmlc, m) {
   m.def("ffm_staged_row_entries", []() { return gpu::kFFMStagedRowEntries; },
         "entries of a row FF1 / FF2 stage in LDS; longer rows re-read global memory");
   m.def(
+      "qid_flags",
+      [stream_of](uintptr_t qid, size_t rows, uintptr_t flag, uintptr_t partials, uintptr_t total,
+                  uintptr_t stream) {
+        // Q1 and the scan of its flags: flag[r] becomes the group of a row that
+        // starts a run, *total the number of groups
+        auto* f = Ptr<uint64_t>(flag);
+        gpu::LaunchQidFlags(Ptr<const uint64_t>(qid), rows, f, stream_of(stream));
+        gpu::LaunchScanU64(f, rows, Ptr<uint64_t>(partials), Ptr<uint64_t>(total),
+                           stream_of(stream));
+      },
+      py::arg("qid"), py::arg("rows"), py::arg("flag"), py::arg("partials"), py::arg("total"),
+      py::arg("stream"));
+  m.def(
+      "qid_group_ptr",
+      [stream_of](uintptr_t qid, size_t rows, uintptr_t scanned, uintptr_t total,
+                  uint64_t capacity, uintptr_t group_ptr, uintptr_t stream) {
+        gpu::LaunchQidGroupPtr(Ptr<const uint64_t>(qid), rows, Ptr<const uint64_t>(scanned),
+                               Ptr<const uint64_t>(total), capacity, Ptr<uint64_t>(group_ptr),
+                               stream_of(stream));
+      },
+      py::arg("qid"), py::arg("rows"), py::arg("scanned"), py::arg("total"), py::arg("capacity"),
+      py::arg("group_ptr"), py::arg("stream"));
+  m.def("qid_scan_words", [](size_t rows) { return gpu::ScanPartials(rows) + 1; }, py::arg("rows"),
+        "u64 words of scan scratch qid_flags needs next to its `rows` flags");
+  m.def(
+      "rank_loss",
+      [stream_of](uintptr_t score, uintptr_t label, uintptr_t group_ptr, size_t groups,
+                  uint64_t rows, bool ndcg_weights, float sigma, uintptr_t row_scratch,
+                  uintptr_t grad, uintptr_t loss_g, uintptr_t pairs_g, uintptr_t error,
+                  uintptr_t stream) {
+        gpu::LaunchRankLoss(Ptr<const float>(score), Ptr<const float>(label),
+                            Ptr<const uint64_t>(group_ptr), groups, rows, ndcg_weights, sigma,
+                            Ptr<float>(row_scratch), Ptr<float>(grad), Ptr<float>(loss_g),
+                            Ptr<int64_t>(pairs_g), Ptr<int>(error), stream_of(stream));
+      },
+      py::arg("score"), py::arg("label"), py::arg("group_ptr"), py::arg("groups"), py::arg("rows"),
+      py::arg("ndcg_weights"), py::arg("sigma"), py::arg("row_scratch"), py::arg("grad"),
+      py::arg("loss_g"), py::arg("pairs_g"), py::arg("error"), py::arg("stream"));
+  m.def(
+      "rank_ndcg",
+      [stream_of](uintptr_t score, uintptr_t label, uintptr_t group_ptr, size_t groups,
+                  uint64_t rows, uint32_t k, uintptr_t ndcg, uintptr_t error, uintptr_t stream) {
+        gpu::LaunchRankNdcg(Ptr<const float>(score), Ptr<const float>(label),
+                            Ptr<const uint64_t>(group_ptr), groups, rows, k, Ptr<float>(ndcg),
+                            Ptr<int>(error), stream_of(stream));
+      },
+      py::arg("score"), py::arg("label"), py::arg("group_ptr"), py::arg("groups"), py::arg("rows"),
+      py::arg("k"), py::arg("ndcg"), py::arg("error"), py::arg("stream"));
+  m.def("rank_wave_group_rows", []() { return gpu::kRankWaveGroupRows; },
+        "rows of a group RK1 (one wave per group) takes; longer groups run on RK2");
+  m.def("rank_tile_rows", []() { return gpu::kRankTileRows; },
+        "rows of the tiles RK2 passes a long group through LDS in");
+  m.def("rank_max_label", []() { return gpu::kRankMaxLabel; },
+        "largest label ops.rank_loss / ops.ndcg take");
+  m.attr("rank_err_group") = gpu::kRankErrGroup;
+  m.attr("rank_err_label") = gpu::kRankErrLabel;
+  m.def(
       "csr_transpose",
       [stream_of](const CsrArg& csr, uint64_t base, uint64_t nnz, uint64_t num_features,
                   uintptr_t col_ptr, uintptr_t row_out, uintptr_t val_out, uintptr_t scratch,
