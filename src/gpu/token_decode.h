@@ -9,9 +9,8 @@
  *  consecutive tokens (about 16 B apart), so the four 16-lane groups of a
  *  ds_read_b128 read nearly disjoint bank quads -- the unaligned dword reads
  *  of the round-2 kernel were 4-way conflicted at that stride.
- *  Digit runs are decoded 4 bytes at a time (SWAR, lead_digits); every
- *  number takes one window, a value's fraction digits come out of the same
- *  window when they fit.
+ *  Digit runs are decoded 8 bytes at a time (SWAR, digit_run8) from a
+ *  12-byte window (ext12) at the run's own start.
  *
  *  Arithmetic parity with src/data/strtonum.h (reference src/data/strtonum.h:
  *  37-97): an integer part of <= 7 digits accumulated in float is exact, so it
@@ -20,7 +19,10 @@
  *  k <= 8 (the quotient's distance to a float rounding boundary exceeds the
  *  double rounding error), and for k <= 7 (F < 2^24, exact in float) that
  *  quotient is q0 = F * r, q1 = fma(F - q0 * 10^k, r, q0) with r = RN(1 / 10^k)
- *  -- checked exhaustively for every F < 10^k, k = 1..7.  Shapes outside the
+ *  -- checked exhaustively for every F < 10^k, k = 1..7
+ *  (tests/test_gpu_number_decode.py holds the kernels to it, bit for bit: every
+ *  F for k <= 5, for k = 6, 7 the F nearest to a rounding boundary and those
+ *  that q0 alone gets wrong; corpora in tests/number_cases.py).  Shapes outside the
  *  fast path (exponents, > 7 integer or fraction digits, over-long indices,
  *  signs on indices, tokens longer than the windows) return false and take
  *  the generic ParsePair / ParseTriple.
@@ -57,48 +59,6 @@ __device__ __forceinline__ uint32_t pow10_u(uint32_t k) {
   const uint32_t b = (k & 2u) ? 100u : 1u;
   const uint32_t c = (k & 4u) ? 10000u : 1u;
   return __umul24(__umul24(a, b), c);
-}
-
-/*!
- * \brief SWAR: number of leading ASCII digits (0..4) of the 4 bytes g (first
- *  byte = lowest) and their decimal value.
- */
-__device__ __forceinline__ uint32_t lead_digits(uint32_t g, uint32_t* val) {
-  const uint32_t lo4 = g & 0x0F0F0F0Fu;
-  const uint32_t hi = (g & 0xF0F0F0F0u) ^ 0x30303030u;        // high nibble != 3
-  const uint32_t lo = (lo4 + 0x06060606u) & 0x10101010u;      // low nibble > 9
-  const uint32_t bad = hi | (lo << 3);
-  // no non-digit byte: 4 digits
-  const uint32_t k = static_cast<uint32_t>(__builtin_ctzg(bad, 32)) >> 3;
-  // k digits right-aligned (a 64-bit shift: k = 0 shifts them all out)
-  const uint32_t x = static_cast<uint32_t>((static_cast<uint64_t>(lo4) << (8u * (4u - k))));
-  // digit pairs by byte dot products (v_dot4_u32_u8), then pair0 * 100 + pair1
-  const uint32_t p0 = __builtin_amdgcn_udot4(x, 0x0000010Au, 0u, false);
-  const uint32_t p1 = __builtin_amdgcn_udot4(x, 0x010A0000u, 0u, false);
-  *val = __umul24(p0, 100u) + p1;
-  return k;
-}
-
-/*!
- * \brief the value and digit count of a run split in two 4-byte groups:
- *  (k0, v0) the first group's lead_digits, (k1, v1) the second's, which
- *  counts only when the first is full.  The empty asm pins the second group
- *  as computed: left alone, hipcc sinks it into an exec-masked branch (an
- *  s_and_saveexec / s_cbranch_execz / exec restore per number, and no
- *  interleaving of independent numbers across it).  Both factors are below
- *  2^24: a full-rate v_mul_u32_u24, not the quarter-rate v_mul_lo_u32.
- */
-__device__ __forceinline__ uint32_t join_groups(uint32_t k0, uint32_t v0, uint32_t k1, uint32_t v1,
-                                                uint32_t* k) {
-  // (an explicit v_mul_u32_u24: from __umul24 of operands it can bound,
-  // hipcc emits the quarter-rate v_mul_lo_u32)
-  uint32_t x;
-  asm("v_mul_u32_u24 %0, %1, %2" : "=v"(x) : "v"(v0), "v"(pow10_u(k1)));
-  x += v1;
-  asm("" : "+v"(x));
-  const bool full = k0 == 4;
-  *k = full ? 4u + k1 : k0;
-  return full ? x : v0;
 }
 
 /*!
@@ -198,14 +158,10 @@ struct Num {
   bool ok_float, ok_uint;
 };
 
-__device__ __forceinline__ Num parse_num_g(uint4 g, uint32_t a);
-
 /*!
  * \brief parse_num on LDS: the integer digits from a 12-byte window at the
  *  number, the fraction from a second one at the byte after the '.' (read
- *  unconditionally: branch-free), each decoded by digit_run8.  The same
- *  values and flags as parse_num_g on every number whose fraction fits its
- *  16-byte window; a longer fraction (<= 7 digits) is taken here as well.
+ *  unconditionally: branch-free), each decoded by digit_run8.
  *  Two extensions run only when some lane of the wave needs them (wave-
  *  uniform branches: free on plain `0.dddddd` data), with parse_num_ext's
  *  arithmetic, so the values are the same bits: fractions of 8 to 15 digits
@@ -279,63 +235,6 @@ __device__ __forceinline__ Num parse_num(const uint4* lds, uint32_t a) {
       v = eneg ? (v / scale) : (v * scale);
     }
   }
-  o.fval = neg ? -v : v;
-  return o;
-}
-
-/*! \brief parse_num on the 16 bytes g already read from LDS byte a */
-__device__ __forceinline__ Num parse_num_g(uint4 g, uint32_t a) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
-  Num o;
-  const uint32_t c0 = g.x & 0xFFu;
-  const bool neg = c0 == '-';
-  const uint32_t s = (neg || c0 == '+') ? 1u : 0u;
-  const uint32_t h0 = __builtin_amdgcn_alignbyte(g.y, g.x, s);
-  const uint32_t h1 = __builtin_amdgcn_alignbyte(g.z, g.y, s);
-  const uint32_t h2 = __builtin_amdgcn_alignbyte(g.w, g.z, s);
-  const uint32_t h3 = g.w >> (8u * s);
-  // integer digits (<= 8) and the byte after them
-  uint32_t v0, v1;
-  const uint32_t k0 = lead_digits(h0, &v0);
-  const uint32_t k1 = lead_digits(h1, &v1);
-  uint32_t k;
-  const uint32_t iv = join_groups(k0, v0, k1, v1, &k);
-  const uint32_t tw = k < 4 ? h0 : (k < 8 ? h1 : h2);
-  const uint32_t term = (tw >> (8u * (k & 3u))) & 0xFFu;
-  // fraction digits: 8 bytes at fs = k + 1 (1..9) of h0..h3
-  const uint32_t fs = k + 1u;
-  const uint32_t q = fs >> 2, r = fs & 3u;
-  const uint32_t a0 = q == 0 ? h0 : (q == 1 ? h1 : h2);
-  const uint32_t a1 = q == 0 ? h1 : (q == 1 ? h2 : h3);
-  const uint32_t a2 = q == 0 ? h2 : (q == 1 ? h3 : 0u);
-  const uint32_t lo = __builtin_amdgcn_alignbyte(a1, a0, r);
-  const uint32_t hi = __builtin_amdgcn_alignbyte(a2, a1, r);
-  uint32_t w0, w1;
-  const uint32_t f0 = lead_digits(lo, &w0);
-  const uint32_t f1 = lead_digits(hi, &w1);
-  uint32_t nf;
-  const uint32_t fv = join_groups(f0, w0, f1, w1, &nf);
-  const uint32_t fw = nf < 4 ? lo : hi;
-  const uint32_t fterm = nf < 8 ? (fw >> (8u * (nf & 3u))) & 0xFFu : 0x30u;
-  const bool dot = term == '.';
-  // the fraction and its terminator must lie inside the 16 - s window bytes
-  const bool frac_ok = (nf <= 7) & (fs + nf < 16u - s) & ((k | nf) != 0);
-  o.ok_float = (k <= 7) & (dot ? frac_ok : k != 0);
-  o.ok_uint = (s == 0) & !dot & (k != 0) & !((k == 8) & ((h2 & 0xFFu) - '0' < 10u));
-  o.term = dot ? fterm : term;
-  o.end = a + s + k + (dot ? 1u + nf : 0u);
-  o.ival = iv;
-  // StrToFloat: float(int digits) + float(F / 10^nf) (see file comment)
-  float p, inv;
-  pow10f(nf, &p, &inv);
-  const float ff = static_cast<float>(fv);
-  const float q0 = ff * inv;
-  const float rem = __builtin_fmaf(-q0, p, ff);
-  const float frac = __builtin_fmaf(rem, inv, q0);
-  float v = static_cast<float>(iv);
-  v = dot ? v + frac : v;
   o.fval = neg ? -v : v;
   return o;
 }

@@ -30,7 +30,9 @@ def cpu_rows(uri, fmt, nparts=1, index64=False):
 
 
 def assert_same(a, b, field=False):
-    for k in ("label", "weight", "qid", "offset", "index", "value"):
+    for k in ("label", "weight", "value"):  # as bits: -0 is not 0
+        np.testing.assert_array_equal(a[k].view(np.uint32), b[k].view(np.uint32), err_msg=k)
+    for k in ("qid", "offset", "index"):
         np.testing.assert_array_equal(a[k], b[k], err_msg=k)
     if field:
         np.testing.assert_array_equal(a["field"], b["field"])
