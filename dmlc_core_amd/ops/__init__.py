@@ -750,7 +750,9 @@ def qid_groups(qid: torch.Tensor) -> torch.Tensor:
         return torch.zeros(1, dtype=torch.int64, device=dev)
     words = rows + int(_dmlc.qid_scan_words(rows)) + 1
     ws = _workspace(8 * words + 16, dev)
-    flag = (_ptr(ws) + 15) // 16 * 16  # the scan's 16-byte loads
+    # the scan reads its data, the flags, by 16-byte loads; its partials and
+    # total are single-word accesses and follow the flags wherever they end
+    flag = (_ptr(ws) + 15) // 16 * 16
     partials, total = flag + 8 * rows, flag + 8 * (words - 1)
     stream = _stream()
     _dmlc.qid_flags(_ptr(qid), rows, flag, partials, total, stream)

@@ -153,7 +153,13 @@ void LaunchTextCount(const char* text, size_t nbytes, const uint32_t* line_start
                      MetaPartial* partials, ChunkMeta* meta, hipStream_t stream);
 
 /*!
- * \brief K3: exclusive scan of n u64 values in place; *total receives the sum.
+ * \brief K3: exclusive scan of n u64 values in place (mod 2^64); *total
+ *  receives the sum.
+ *
+ *  Alignment: `data` must be 16-byte aligned -- the reduce and down-sweep
+ *  passes read and write it as 16-byte pairs.  `partials` and `total` need
+ *  only the 8 bytes of a u64: every access to them is a single word, so a
+ *  caller may place them straight behind an array of any length.
  * \param partials >= ScanPartials(n) + 1 u64
  */
 void LaunchScanU64(uint64_t* data, size_t n, uint64_t* partials, uint64_t* total,

@@ -3,9 +3,10 @@
  * \brief K3: device-wide exclusive scan of u64 (reduce -> scan partials ->
  *  down-sweep), used for line offsets and CSR row pointers.
  *
- * 256-thread workgroups, 8 elements per lane (2048 per tile), 16-byte loads.
- * The partial sums are scanned by a single workgroup that walks them in
- * 2048-wide tiles, so any n works without recursion.
+ * 256-thread workgroups, 8 elements per lane (2048 per tile), 16-byte loads
+ * and stores of the data.  The partial sums are scanned by a single workgroup
+ * that walks them in 2048-wide tiles, so any n works without recursion; they
+ * are touched by 8-byte accesses only (kernels.h: the alignment contract).
  */
 #include <hip/hip_runtime.h>
 
@@ -20,6 +21,15 @@ constexpr int kThreads = 256;
 constexpr int kPer = 8;
 constexpr size_t kTile = kThreads * kPer;
 
+/*! \brief 8 words from `base` (0 past n) by 8-byte accesses: `in` needs no
+ *  more than a u64's alignment */
+__device__ __forceinline__ void load8_words(const uint64_t* in, size_t base, size_t n,
+                                            uint64_t (&v)[kPer]) {
+#pragma unroll
+  for (int i = 0; i < kPer; ++i) v[i] = base + i < n ? in[base + i] : 0;
+}
+
+/*! \brief the same by 16-byte loads where all 8 words exist: `in` 16-byte aligned */
 __device__ __forceinline__ void load8(const uint64_t* in, size_t base, size_t n, uint64_t (&v)[kPer]) {
   if (base + kPer <= n) {
     const ulonglong2* p = reinterpret_cast<const ulonglong2*>(in + base);
@@ -30,8 +40,7 @@ __device__ __forceinline__ void load8(const uint64_t* in, size_t base, size_t n,
       v[2 * i + 1] = t.y;
     }
   } else {
-#pragma unroll
-    for (int i = 0; i < kPer; ++i) v[i] = base + i < n ? in[base + i] : 0;
+    load8_words(in, base, n, v);
   }
 }
 
@@ -55,7 +64,9 @@ __global__ __launch_bounds__(kThreads) void k_scan_partials(uint64_t* __restrict
   for (size_t t = 0; t < np; t += kTile) {
     const size_t base = t + threadIdx.x * kPer;
     uint64_t v[kPer];
-    load8(partials, base, np, v);
+    // one workgroup over n / 2048 words: callers place `partials` behind an
+    // array of any length, so it is read and written as single u64
+    load8_words(partials, base, np, v);
     uint64_t s = 0;
 #pragma unroll
     for (int i = 0; i < kPer; ++i) s += v[i];
