@@ -537,7 +537,13 @@ __attribute__((amdgpu_waves_per_eu(6))) void k_csv_tile_fill(const uint8_t* __re
       const uint4 v = at + 16 <= n ? pv : load16_clip(text, at, n);
       const uint32_t nslot = ((s + 1) & 1u) * (kStep / 16);
       ring[nslot + lane] = v;
-      if (nslot == 0 && lane < 2) ring[2 * kStep / 16 + lane] = v;
+      // the last step (slot 1) stages nothing behind it: its mirror is zeroed
+      // here, while slot 0 is walked (whose reads end in slot 1).  A chunk that
+      // ends with the last step reads its last field on into the mirror: the
+      // zeros past the chunk, not the head of step kMaxSteps - 2
+      if (lane < 2 && (nslot == 0 || s + 2 == kMaxSteps)) {
+        ring[2 * kStep / 16 + lane] = nslot == 0 ? v : make_uint4(0u, 0u, 0u, 0u);
+      }
       if (s + 2 < kMaxSteps) {
         const size_t at2 = at + kStep;
         pv = *reinterpret_cast<const uint4*>(text + (at2 + 16 <= n ? at2 : 0));

@@ -165,7 +165,20 @@ def parse_libfm(text: str):
     return rows
 
 
-def parse_csv(text: str, label_column=-1, delim=","):
+_FIELD_VALUES = {}
+
+
+def _field_value(f: str) -> float:
+    v = _FIELD_VALUES.get(f)
+    if v is None:
+        v = _FIELD_VALUES[f] = strtof(f.lstrip(" \t\r\n\f"))
+    return v
+
+
+def parse_csv(text: str, label_column=-1, delim=",", weight_column=-1):
+    """rows (label, features); with a weight column (src/data/csv_parser.h:
+    the label column is tested first, a row without the column weighs 1.0)
+    rows (label, features, weight)"""
     rows = []
     for line in _lines(text):
         fields = line.split(delim)
@@ -173,15 +186,17 @@ def parse_csv(text: str, label_column=-1, delim=","):
         # when p reaches the line end, so a trailing delimiter adds no field
         if len(fields) > 1 and fields[-1] == "":
             fields.pop()
-        lab = 0.0
+        lab, wgt = 0.0, 1.0
         feats = []
         for c, f in enumerate(fields):
-            v = strtof(f.lstrip(" \t\r\n\f"))
+            v = _field_value(f)
             if c == label_column:
                 lab = v
+            elif c == weight_column:
+                wgt = v
             else:
                 feats.append(v)
-        rows.append((lab, feats))
+        rows.append((lab, feats, wgt) if weight_column >= 0 else (lab, feats))
     return rows
 
 
