@@ -1035,6 +1035,7 @@ __global__ __launch_bounds__(kThreads, DMLC_FILL_WAVES) void k_tile_fill(
       clamp32(static_cast<int64_t>(out.nnz_limit) - static_cast<int64_t>(C));
   const int32_t row_room =
       clamp32(static_cast<int64_t>(out.row_limit) - static_cast<int64_t>(R));
+  const uint32_t nnz_room_u = nnz_room > 0 ? static_cast<uint32_t>(nnz_room) : 0u;
   IndexType* const idx_at = out.index + C;
   float* const val_at = out.value + C;
   IndexType* const fld_at = out.field != nullptr ? out.field + C : nullptr;
@@ -1180,7 +1181,13 @@ __global__ __launch_bounds__(kThreads, DMLC_FILL_WAVES) void k_tile_fill(
       const uint32_t lc = e >> 14;
       const int32_t rel = static_cast<int32_t>(i) - static_cast<int32_t>(lc);
       const bool row_ok = static_cast<int32_t>(lc) - 1 < row_room;
-      const bool nnz_ok = rel < nnz_room;
+      // rel < 0: the tile opens with a line that counts while its first token
+      // does not start it -- a letter token taken out of the list (qid chunk),
+      // or, in one pass (where no count pass has turned the chunk away), a
+      // blank-started or blank-only line.  Both are flagged irregular; the
+      // feature must not be stored, its unsigned byte offset below would
+      // wrap.  One unsigned compare covers 0 <= rel < room.
+      const bool nnz_ok = static_cast<uint32_t>(rel) < nnz_room_u;
       bool field_ok = true;
       if (F == TextFormat::kLibFM) field_ok = is_label || t.r >= 2;
       // past the target's rows / entries: with sizes from C1 + C2 that is a
