@@ -22,7 +22,7 @@
  *                         position -- line ends and delimiters only, 8 loads
  *                         in flight, no walk; the fill adds its tile's head
  *                         fields and does S1's checks;
- *   C2 (tile_kernels.hip, raw scan), then
+ *   C2 (tile_count_kernels.hip, raw scan), then
  *   S2 k_csv_tile_fill  : the same walk over a two-step LDS ring (one step
  *                         prefetched, so a number's 16-byte window never
  *                         leaves LDS); the step's fields are listed in LDS and
@@ -31,7 +31,7 @@
  *                         shapes go through strtonum.h's StrToFloat from
  *                         global memory); row starts write the row pointer,
  *                         a row's last field settles a missing label / weight;
- *   C4 (tile_kernels.hip) folds max index / flags and closes the offsets.
+ *   C4 (tile_count_kernels.hip) folds max index / flags and closes the offsets.
  */
 #include <dmlc/logging.h>
 #include <hip/hip_runtime.h>

@@ -272,6 +272,21 @@ __device__ __forceinline__ void block_store_partial(unsigned long long mi, unsig
 }
 
 /*!
+ * \brief the workgroup's group ordinal of a one-pass launch, in ticket order
+ *  (not dispatch order): a workgroup looks back only at tiles of workgroups
+ *  that started before it, so every tile it waits on is resident or done.
+ *  ticket0: the counter's value before the launch.  Every thread of the
+ *  workgroup calls it (one barrier).
+ */
+__device__ __forceinline__ uint32_t ticket_group(unsigned long long* ticket,
+                                                 unsigned long long ticket0) {
+  __shared__ uint32_t s_ticket;
+  if (threadIdx.x == 0) s_ticket = static_cast<uint32_t>(atomicAdd(ticket, 1ull) - ticket0);
+  __syncthreads();
+  return s_ticket;
+}
+
+/*!
  * \brief decoupled look-back over per-tile count pairs -- the one-pass
  *  kernels' replacement of a count kernel + scan.  Word: state (1: this tile's
  *  own counts, 2: inclusive prefix; 0: not yet -- the array is zeroed by a

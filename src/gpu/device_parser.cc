@@ -6,8 +6,9 @@
  *  copy / unpack streams and their events, the HBM epoch cache); each chunk is
  *  acquired from it, parsed here and released.
  *
- * LibSVM / LibFM chunks take the LDS-staged tile parser (tile_kernels.hip:
- * C1 count, C2 scan, C3 fill, C4 finish; lane per token, SWAR number decode).
+ * LibSVM / LibFM chunks take the LDS-staged tile parser (tile_count_kernels.hip:
+ * C1 count, C2 scan, C4 finish; tile_fill_kernels.hip: C3 fill; lane per token,
+ * SWAR number decode).
  * A chunk it flags as irregular (qid tokens, digit-less tokens, label-less
  * lines, control bytes), and every CSV chunk the CSV tile kernels
  * (csv_kernels.hip) flag, is parsed by the exact wave-per-line kernels
@@ -364,7 +365,7 @@ class DeviceParserImpl : public DeviceParser<IndexType> {
   }
 
   /*!
-   * \brief LDS-staged tile parse (tile_kernels.hip); false when the chunk must
+   * \brief LDS-staged tile parse (tile_common.h); false when the chunk must
    *  take the exact path.  One blocking read-back (the chunk's sizes) before
    *  the fill, one for the maxima / flags after it.
    */

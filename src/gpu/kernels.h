@@ -10,6 +10,9 @@
  *   K5 CSV / K6 LibFM    same launchers, TextFormat::kCSV / kLibFM
  *   K7 recordio decode   LaunchRecordIOTileCount / LaunchRecordIOTileFill, LaunchRecordIOGather
  *                        (recordio_kernels.hip)
+ *   C1 + C2 tile count   LaunchTileCountScan, LaunchTileScanRaw (tile_count_kernels.hip)
+ *   C3 tile fill / hash  LaunchTileFill, LaunchTileHashed (tile_fill_kernels.hip)
+ *   C4 tile finish       LaunchTileFinish         (tile_count_kernels.hip)
  *   K8 max reduce        fused into K4 (wave max + one atomicMax per wave)
  *   K9 fp8 pack / hash   LaunchHashedDenseFP8     (feature_kernels.hip)
  *   K10 csr concat       LaunchCSRAppend          (feature_kernels.hip)

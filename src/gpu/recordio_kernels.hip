@@ -19,7 +19,7 @@
  *   R1 k_rec_tile_count: one wave per 1024-word (4 KiB) tile, 4 coalesced
  *      16 B loads per lane in flight; (heads << 32 | bytes) per tile and
  *      error bits (a part running past the chunk, a bad cflag).
- *   C2 (tile_kernels.hip, raw mode): exclusive scan, totals published.
+ *   C2 (tile_count_kernels.hip, raw mode): exclusive scan, totals published.
  *   R2 k_rec_tile_fill: the same tile walk; per 1 KiB sub-tile a wave scan
  *      places each part; head parts write their record's offset; parts up to
  *      64 B are copied by the lane that found them, longer ones go to a
@@ -27,7 +27,7 @@
  *      when source and destination allow it).  Every part checks the part
  *      that follows it (a continuation must follow a first / middle part,
  *      a head must follow a whole / last part).
- *   C4 (tile_kernels.hip): error bits folded, closing offset, published.
+ *   C4 (tile_count_kernels.hip): error bits folded, closing offset, published.
  *   One pass (HBM-resident replays): R2 with R1 inside -- each wave counts
  *      its tile from the words it already holds and takes the tiles before it
  *      by decoupled look-back, so a replayed chunk is one launch that reads
@@ -295,15 +295,7 @@ __global__ __launch_bounds__(kThreads) void k_rec_tile_fill(const uint32_t* __re
   const int lane = lane_id();
   const int wave = threadIdx.x / kWave;
   size_t group = blockIdx.x;
-  if constexpr (kOnePass) {
-    // tiles in ticket order: a workgroup looks back only at tiles of
-    // workgroups that started before it, so every tile it waits on is
-    // resident or done
-    __shared__ uint32_t s_ticket;
-    if (threadIdx.x == 0) s_ticket = static_cast<uint32_t>(atomicAdd(op.ticket, 1ull) - op.ticket0);
-    __syncthreads();
-    group = s_ticket;
-  }
+  if constexpr (kOnePass) group = ticket_group(op.ticket, op.ticket0);  // tiles in ticket order
   const size_t tile = group * kWaves + wave;
   if (tile >= ntiles) return;  // whole waves leave; nothing below synchronises waves
   BigPart* big = s_big[wave];

@@ -1,7 +1,7 @@
 /*!
  * \file src/gpu/token_decode.h
  * \brief Register-window decoding of one LibSVM / LibFM token on gfx950 (the
- *  fast path of the tile fill kernel, src/gpu/tile_kernels.hip).
+ *  fast path of the tile fill kernel, src/gpu/tile_fill_kernels.hip).
  *
  *  A token's bytes are read from the LDS-staged text 16 at a time: two
  *  16-byte-aligned ds_read_b128 cover any 16-byte window, which is then

@@ -1,7 +1,7 @@
 """LibSVM / LibFM texts that put line ends, token starts, whole tokens, decode
 rounds, `qid:` tokens, owned lines and the chunk end on every edge of the token
-tile path (src/gpu/tile_kernels.hip: k_tile_count, k_tile_fill, k_tile_hash),
-and a small model of the walk's step accounting.
+tile path (src/gpu/tile_count_kernels.hip: k_tile_count; tile_fill_kernels.hip:
+k_tile_fill, k_tile_hash), and a small model of the walk's step accounting.
 
 Helper of test_svm_cases_cpu.py and test_gpu_svm_edges.py.  Pure Python and
 numpy, deterministic, built once per process.  Every file is ONE chunk for the
@@ -27,7 +27,7 @@ import pyref
 # the geometry of the walk, each next to its source
 TILE = 8192            # kTileBytes (src/gpu/kernels.h): one wave per tile
 COUNT_STRIDE = 1024    # k_tile_count: load j of a lane is at j * 1024 (kCountLoads)
-STEP = 2048            # kStepBytes (tile_kernels.hip): a tile is staged in 4 steps
+STEP = 2048            # kStepBytes (tile_common.h): a tile is staged in 4 steps
 HALF = 1024            # the `a` and `b` slices of a lane: bload16(trs, loff [+ 1024])
 LANE = 16              # bytes of a lane's slice (one 16 B load)
 TAIL = 64              # kSlotBytes = kStepBytes + 64: the bytes staged behind a step

@@ -1,5 +1,5 @@
-"""The token tile path (src/gpu/tile_kernels.hip: k_tile_count, k_tile_fill,
-k_tile_hash) on the placed cases of svm_cases.py: line ends, token starts,
+"""The token tile path (src/gpu/tile_count_kernels.hip: k_tile_count;
+tile_fill_kernels.hip: k_tile_fill, k_tile_hash) on the placed cases of svm_cases.py: line ends, token starts,
 whole tokens, decode-round totals, deferred tokens, weights, `qid:` tokens,
 owned lines and the chunk end on every lane, half-step, step and tile edge of
 the walk, LibSVM and LibFM.
