@@ -26,7 +26,7 @@ import sys
 __version__ = "0.1.0"
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_SUBMODULES = ("utils", "io", "data", "ops", "parallel", "models")
+_SUBMODULES = ("utils", "io", "data", "ops", "parallel", "models", "optim")
 
 
 def _load_native():

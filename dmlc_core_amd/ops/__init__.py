@@ -2,7 +2,8 @@
 
 Every op launches a hand-written CDNA4 kernel from ``libdmlc.so`` on the
 current torch stream (src/gpu/feature_kernels.hip, spmm_kernels.hip,
-transpose_kernels.hip, gather_kernels.hip, ffm_kernels.hip, rank_kernels.hip).
+transpose_kernels.hip, gather_kernels.hip, ffm_kernels.hip, rank_kernels.hip,
+compact_kernels.hip, optim_kernels.hip).
 There is no PyTorch fallback: on a machine without the extension or a GPU these
 functions raise.
 
@@ -20,6 +21,7 @@ from .. import _dmlc
 
 __all__ = ["spmv", "spmv_t", "hashed_dense", "SpMVFunction", "csr_spmv", "transpose",
            "gather_rows", "gather_buffers", "release_workspace",
+           "compact_features", "lazy_update_",
            "spmm", "spmm_t", "SpMMFunction", "csr_spmm",
            "ffm", "ffm_t", "FFMFunction", "csr_ffm",
            "qid_groups", "group_rows", "rank_loss", "rank_loss_parts", "RankLossFunction", "ndcg"]
@@ -941,6 +943,231 @@ def ndcg(score: torch.Tensor, label: torch.Tensor, group_ptr: torch.Tensor,
     if validate:
         _raise_rank_errors("ndcg", err, rows)
     return out
+
+
+_INDEX_DTYPES = (torch.int32, torch.uint32, torch.int64, torch.uint64)
+_BATCH_COLUMNS = ("label", "weight", "qid", "group_ptr")  # passed through by compact_features
+
+
+def _narrow_fields(field: torch.Tensor) -> torch.Tensor:
+    """a slice of a ``field`` column as int32, the compact ``index``'s dtype:
+    32-bit columns are reinterpreted, 64-bit ones converted, a field that does
+    not fit becoming -1 (2^32 - 1 to the kernels: never a valid field)"""
+    if field.element_size() == 4:
+        return field if field.dtype == torch.int32 else field.view(torch.int32)
+    f = field if field.dtype == torch.int64 else field.view(torch.int64)
+    return torch.where((f < 0) | (f > 0x7FFFFFFF), torch.full_like(f, -1), f).to(torch.int32)
+
+
+def compact_features(csr: Dict, num_features: int, validate: bool = True) -> Dict:
+    """The batch with its feature ids renumbered to ``0 .. U-1``, U the number
+    of distinct ids among its entries (U1 - U4, src/gpu/compact_kernels.hip):
+    every CSR op then works on a ``[U, ...]`` slice of the parameters
+    (``w[batch["ids"]]``) and returns compact ``[U, ...]`` gradients.
+
+    ``csr``: a ``csr_to_torch`` / ``gather_rows`` dict or a row slice
+    (``offset[b:e + 1]`` next to the whole ``index``: only the entries of the
+    slice's rows count); 32- or 64-bit indices; a transpose's pair views are
+    unpaired first.  ``num_features``: an int from 1 to
+    ``_dmlc.compact_max_features()`` (2^32); the batch must have fewer than
+    2^31 entries.  Anything else raises ``ValueError`` before a launch.
+
+    Returns a batch dict: ``ids`` int64 ``[U]`` strictly ascending, ``index``
+    int32 ``[nnz]`` (each entry's position in ``ids``, for 64-bit sources too),
+    ``offset`` int64 ``[rows + 1]`` from 0 (a view of a buffer one slot larger,
+    as :func:`gather_buffers` makes them: the "auto" gradient policy then keeps
+    the atomic form for a batch made per step), ``value`` (the source's slice,
+    None stays None), ``field`` if the source dict has one (the source's slice
+    as int32, ``index``'s dtype), ``label`` / ``weight`` / ``qid`` /
+    ``group_ptr`` passed through, and ``num_features`` = U.
+
+    No sort: U1 sets a bit per touched id in a bitmap of ``num_features`` bits
+    (testing the bit by a load before any atomic), U2 counts the bits of every
+    64-bit word, the K3 scan numbers them, U3 writes the ids and U4 every
+    entry's slot.  The bitmap, counts and scan scratch -- about
+    ``num_features / 4`` bytes, ``_dmlc.compact_scratch_bytes()`` -- live in
+    the persistent workspace of :func:`transpose` and the bitmap is cleared in
+    the stream on every call.  The atomics build a set, so the output bytes are
+    a pure function of the inputs.
+
+    At most two device-to-host reads per call: the slice's ends
+    ``offset[[0, -1]]`` (as :func:`transpose`), and one 16-byte copy holding U
+    and the error word, between the scan and U3 (it sizes ``ids``).  An id
+    ``>= num_features`` forms no address and is flagged: ``validate=True``
+    raises ``ValueError``; ``validate=False`` does not, such an entry gets slot
+    0 and what it contributes to a product or a gradient is unspecified (with
+    U = 0 nothing may be indexed: it raises either way).  A batch without rows
+    or entries gives U = 0 without a launch."""
+    if isinstance(num_features, bool) or not isinstance(num_features, int):
+        raise ValueError(f"compact_features: num_features must be an int, got {num_features!r}")
+    fmax = int(_dmlc.compact_max_features())
+    if not 1 <= num_features <= fmax:
+        raise ValueError(f"compact_features: num_features must be in [1, {fmax}], "
+                         f"got {num_features}")
+    for k in ("offset", "index"):
+        if not isinstance(csr.get(k), torch.Tensor) or csr[k].dim() != 1:
+            raise ValueError(f"compact_features: csr[{k!r}] must be a 1-D tensor")
+    csr = _unpair(csr)
+    offset, index, value, field = csr["offset"], csr["index"], csr.get("value"), csr.get("field")
+    if offset.dtype not in (torch.int64, torch.uint64) or offset.numel() < 1:
+        raise ValueError("compact_features: csr['offset'] must be a 64-bit row pointer "
+                         "of rows + 1 entries")
+    if index.dtype not in _INDEX_DTYPES:
+        raise ValueError(f"compact_features: csr['index'] must be a 32- or 64-bit integer "
+                         f"tensor, got {index.dtype}")
+    view, nrows = _view(csr)
+    dev = index.device
+    for k, t in (("value", value), ("field", field)):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or not t.is_contiguous() \
+                or t.dim() != 1 or t.device != dev:
+            raise ValueError(f"compact_features: csr[{k!r}] must be a contiguous 1-D tensor "
+                             "on index's device")
+    if field is not None and field.dtype not in _INDEX_DTYPES:
+        raise ValueError(f"compact_features: csr['field'] must be a 32- or 64-bit integer "
+                         f"tensor, got {field.dtype}")
+    off = offset.view(torch.int64) if offset.dtype != torch.int64 else offset
+    lo, hi = (int(v) for v in off[[0, -1]].tolist()) if nrows > 0 else (0, 0)
+    nnz = hi - lo
+    entries = min(t.numel() for t in (index, value, field) if t is not None)
+    if lo < 0 or nnz < 0 or hi > entries:
+        raise ValueError(f"compact_features: csr['offset'] spans entries [{lo}, {hi}) of {entries}")
+    if nnz >= 1 << 31:
+        raise ValueError(f"compact_features: a batch must have fewer than 2^31 entries, has {nnz}")
+    out_offset = torch.zeros(nrows + 2, dtype=torch.int64, device=dev)  # gather_buffers
+    if nnz > 0:
+        ws = _workspace(int(_dmlc.compact_scratch_bytes(num_features)) + 16, dev)
+        scratch = (_ptr(ws) + 15) // 16 * 16
+        status = torch.zeros(2, dtype=torch.int64, device=dev)  # [U, error word]
+        stream = _stream()
+        _dmlc.compact_mark(view, lo, nnz, num_features, scratch, _ptr(status), _ptr(status) + 8,
+                           stream)
+        n_ids, err = status.tolist()
+        if err and (validate or n_ids == 0):
+            raise ValueError(f"compact_features: a feature id is >= num_features ({num_features})")
+        ids = torch.empty(n_ids, dtype=torch.int64, device=dev)
+        slot = torch.empty(nnz, dtype=torch.int32, device=dev)
+        _dmlc.compact_emit(view, lo, nnz, num_features, scratch, n_ids, _ptr(ids), _ptr(slot),
+                           _ptr(out_offset), stream)
+    else:
+        n_ids = 0
+        ids = torch.empty(0, dtype=torch.int64, device=dev)
+        slot = torch.empty(0, dtype=torch.int32, device=dev)
+    res = {"ids": ids, "index": slot, "offset": out_offset[:nrows + 1],
+           "value": None if value is None else value[lo:hi]}
+    if "field" in csr:
+        res["field"] = None if field is None else _narrow_fields(field[lo:hi])
+    for k in _BATCH_COLUMNS:
+        if k in csr:
+            res[k] = csr[k]
+    res["num_features"] = n_ids
+    return res
+
+
+_LAZY_RULES = {"adagrad": (("lr", None), ("eps", 1e-10), ("l2", 0.0)),
+               "ftrl": (("alpha", None), ("beta", 1.0), ("l1", 0.0), ("l2", 0.0))}
+
+
+def _lazy_hyper(rule: str, hyper: Dict) -> list:
+    """the four floats of ``_dmlc.lazy_update`` for ``rule`` from its keyword
+    arguments, checked"""
+    if rule not in _LAZY_RULES:
+        raise ValueError(f"lazy_update_: rule must be one of {sorted(_LAZY_RULES)}, got {rule!r}")
+    spec = _LAZY_RULES[rule]
+    unknown = set(hyper) - {k for k, _ in spec}
+    if unknown:
+        raise ValueError(f"lazy_update_: {rule!r} takes {[k for k, _ in spec]}, "
+                         f"not {sorted(unknown)}")
+    vals = []
+    for k, default in spec:
+        v = hyper.get(k, default)
+        if v is None:
+            raise ValueError(f"lazy_update_: {rule!r} needs {k}=")
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not v == v or v < 0:
+            raise ValueError(f"lazy_update_: {k} must be a number >= 0, got {v!r}")
+        if default is None and not v > 0:
+            raise ValueError(f"lazy_update_: {k} must be > 0, got {v!r}")
+        vals.append(float(v))
+    return vals + [0.0] * (4 - len(vals))
+
+
+def lazy_update_(param: torch.Tensor, ids: Optional[torch.Tensor], grad: torch.Tensor,
+                 state: tuple, rule: str, validate: bool = True, **hyper) -> None:
+    """One optimizer step, in place, on the rows ``ids`` of ``param`` and of
+    its state tensors (L1, src/gpu/optim_kernels.hip): the fused update of a
+    row-sparse minibatch step.  Rows not named in ``ids`` are neither read nor
+    written.
+
+    ``param``: a contiguous float32 device tensor ``[F, ...]`` (width = the
+    product of the trailing dimensions, 1 without); ``ids``: int64 ``[U]``,
+    strictly ascending, every id ``< F`` (:func:`compact_features`'s ``ids``),
+    or None for the dense identity ``0 .. F-1`` (biases, small tensors);
+    ``grad``: contiguous float32 ``[U, ...]`` with ``param``'s trailing shape;
+    ``state``: a tuple of tensors shaped like ``param``.  Anything else raises
+    ``ValueError`` before a launch.  Rules, f32 in exactly this order
+    (``-ffp-contract=off``):
+
+    ``"adagrad"`` (``lr, eps=1e-10, l2=0``), state ``(n,)``::
+
+        g' = g + l2*w;  n += g'*g';  w -= lr * g' / (sqrt(n) + eps)
+
+    torch's ``Adagrad`` with ``lr_decay=0`` and ``initial_accumulator_value=0``.
+    With ``l2 = 0`` lazy steps equal dense steps exactly (an untouched row has
+    gradient 0); with ``l2 > 0`` the decay is applied to a row only when it is
+    touched -- the lazy regularisation of the dmlc CTR learners, not torch's
+    ``weight_decay``.
+
+    ``"ftrl"`` (``alpha, beta=1, l1=0, l2=0``), state ``(z, n)``::
+
+        s = (sqrt(n + g*g) - sqrt(n)) / alpha;  z += g - s*w;  n += g*g
+        w = 0 if |z| <= l1 else -(z - sign(z)*l1) / ((beta + sqrt(n))/alpha + l2)
+
+    One thread per (row, 4 columns) with 16-byte accesses when width % 4 == 0
+    and the tensors are 16-byte aligned, else one per element.  Distinct ids
+    give every element one owner: no atomics, the same inputs give the same
+    bytes.  A row whose id is ``>= F`` or not strictly between its neighbours'
+    ids is skipped and flagged; ``validate=True`` reads the flag (the one
+    device-to-host read) and raises ``ValueError``, ``validate=False`` reads
+    nothing."""
+    vals = _lazy_hyper(rule, hyper)
+    # shapes and dtypes first, then devices and layout: a wrong argument is
+    # named whatever device it is on
+    if not isinstance(param, torch.Tensor) or param.dim() < 1 or param.dtype != torch.float32:
+        raise ValueError("lazy_update_: param must be a float32 tensor [F, ...]")
+    feats, trailing = int(param.shape[0]), tuple(param.shape[1:])
+    width = 1
+    for d in trailing:
+        width *= int(d)
+    if ids is not None and (not isinstance(ids, torch.Tensor) or ids.dim() != 1
+                            or ids.dtype != torch.int64):
+        raise ValueError("lazy_update_: ids must be a 1-D int64 tensor (or None)")
+    nrows = feats if ids is None else int(ids.numel())
+    if not isinstance(grad, torch.Tensor) or grad.dtype != torch.float32 \
+            or tuple(grad.shape) != (nrows,) + trailing:
+        raise ValueError(f"lazy_update_: grad must be float32 of shape "
+                         f"{(nrows,) + trailing}")
+    want = 1 if rule == "adagrad" else 2
+    if not isinstance(state, (tuple, list)) or len(state) != want:
+        raise ValueError(f"lazy_update_: {rule!r} takes a state of {want} tensor(s)")
+    for s in state:
+        if not isinstance(s, torch.Tensor) or s.dtype != torch.float32 or s.shape != param.shape:
+            raise ValueError("lazy_update_: every state tensor must be float32 of param's "
+                             f"shape {tuple(param.shape)}")
+    if not param.is_cuda or not param.is_contiguous():
+        raise ValueError("lazy_update_: param must be a contiguous device tensor")
+    for name, t in (("ids", ids), ("grad", grad), *(("state", s) for s in state)):
+        if t is not None and (not t.is_cuda or not t.is_contiguous() or t.device != param.device):
+            raise ValueError(f"lazy_update_: {name} must be a contiguous tensor on param's device")
+    if nrows == 0 or width == 0:
+        return
+    err = torch.zeros(1, dtype=torch.int32, device=param.device)
+    _dmlc.lazy_update(int(_dmlc.lazy_adagrad if rule == "adagrad" else _dmlc.lazy_ftrl),
+                      _ptr(param), _ptr(ids), _ptr(grad), _ptr(state[0]),
+                      _ptr(state[1]) if want == 2 else 0, feats, nrows, width, *vals,
+                      _ptr(err), _stream())
+    if validate and int(err.item()):
+        raise ValueError(f"lazy_update_: ids must be strictly ascending and < {feats}")
 
 
 def csr_spmv(csr: Dict, w: torch.Tensor, bias: torch.Tensor, grad: str = "auto") -> torch.Tensor:

@@ -28,7 +28,12 @@ def main():
     ap.add_argument("--rows", type=int, default=200_000, help="synthetic rows per rank")
     ap.add_argument("--epochs", type=int, default=3)
     ap.add_argument("--batch-rows", type=int, default=8192)
-    ap.add_argument("--lr", type=float, default=0.5)
+    ap.add_argument("--lr", type=float, default=None,
+                    help="sgd: the step size (default 0.5); lazy-adagrad: lr, "
+                         "lazy-ftrl: alpha (default 0.05)")
+    ap.add_argument("--optimizer", choices=("sgd", "lazy-adagrad", "lazy-ftrl"), default="sgd",
+                    help="lazy-*: row-sparse steps (optim.RowSparseStep) that touch only "
+                         "the batch's features; one process only")
     ap.add_argument("--bucket-mb", type=float, default=64.0)
     ap.add_argument("--shuffle-rows", action="store_true",
                     help="a fresh row permutation of the resident CSR every epoch "
@@ -43,6 +48,11 @@ def main():
 
     info = dist.init()
     rank, world = info["rank"], info["world_size"]
+    lazy = args.optimizer != "sgd"
+    if lazy and world > 1:
+        sys.exit(f"--optimizer {args.optimizer} runs on one process: a row-sparse all-reduce "
+                 f"over {world} ranks needs the union of their feature ids, which is not built")
+    lr = args.lr if args.lr is not None else (0.05 if lazy else 0.5)
     uri = args.uri
     if uri is None:
         uri = os.path.join(tempfile.mkdtemp(prefix="dmlc_ffm_"), "shard.libfm")
@@ -70,7 +80,12 @@ def main():
     model = SparseFFM(num_features, num_fields, rank=args.rank).cuda()
     ops.ffm(t, model.v.detach())  # ids and fields checked once for the shard
     reducer = dist.GradAllReducer(model.parameters(), bucket_mb=args.bucket_mb)
-    opt = torch.optim.SGD(model.parameters(), lr=args.lr)
+    opt = torch.optim.SGD(model.parameters(), lr=lr)
+    stepper = None
+    if lazy:
+        from dmlc_core_amd import optim
+        stepper = optim.RowSparseStep(model, optim.LazyAdagrad(lr) if args.optimizer == "lazy-adagrad"
+                                      else optim.LazyFTRL(lr))
     n = csr.rows
     history = []
     shuffled = None
@@ -91,11 +106,14 @@ def main():
         if shuffled is not None:
             shuffled.set_epoch(epoch)
         for batch in (shuffled if shuffled is not None else file_order()):
-            loss = model.loss(batch)
-            opt.zero_grad(set_to_none=False)
-            loss.backward()
-            reducer.synchronize()
-            opt.step()
+            if stepper is not None:
+                loss = stepper.step(batch)
+            else:
+                loss = model.loss(batch)
+                opt.zero_grad(set_to_none=False)
+                loss.backward()
+                reducer.synchronize()
+                opt.step()
             rows_in = batch["label"].numel()
             tot += float(loss.detach()) * rows_in
             cnt += rows_in

@@ -29,6 +29,11 @@
  *   G1 row gather count  LaunchCSRGatherCount     (gather_kernels.hip)
  *   G2 row gather fill   LaunchCSRGatherFill      (gather_kernels.hip)
  *   CSR -> CSC           LaunchCSRTranspose       (transpose_kernels.hip)
+ *   U1 compact mark      LaunchCompactMark        (compact_kernels.hip)
+ *   U2 compact count     LaunchCompactCount       (compact_kernels.hip; + K3)
+ *   U3 compact emit      LaunchCompactEmit        (compact_kernels.hip)
+ *   U4 compact remap     LaunchCompactRemap       (compact_kernels.hip)
+ *   L1 lazy row update   LaunchLazyUpdate         (optim_kernels.hip)
  * The launchers of K9, K11, M1 / M2, FF1 / FF2, G2 and the transpose take
  * their CSR operand as one CsrView and pick the kernel for its index width
  * (and pair layout) themselves; launch_common.h holds what they share.
@@ -656,6 +661,62 @@ void LaunchCSRGatherFill(const CsrView& src, uint64_t src_entries, const void* r
                          size_t n_sel, uint64_t* out_offset, const uint64_t* total,
                          void* out_index, float* out_value, void* out_field,
                          uint64_t out_capacity, uint32_t* error, hipStream_t stream);
+// ------------- compact feature ids of a batch (compact_kernels.hip) -------------
+/*! \brief largest num_features of U1 - U4 (the bitmap's bits) */
+constexpr uint64_t kCompactMaxFeatures = 1ull << 32;
+/*! \brief bit U1 ORs into its error word: an id >= num_features */
+constexpr uint32_t kCompactErrIndex = 1;
+/*!
+ * \brief bytes of the scratch U1 - U4 share (16-byte aligned): the bitmap of
+ *  num_features bits, one u64 count per bitmap word (scanned in place) and the
+ *  scan's partials -- about num_features / 4 bytes
+ */
+size_t CompactScratchBytes(uint64_t num_features);
+/*!
+ * \brief U1: clear the bitmap (in stream order, on every call), then set bit
+ *  `id` for every entry [base, base + nnz) of csr's index (the rows' range of a
+ *  row slice: entries outside it are not marked).  A set bit is seen by a load
+ *  before any atomic.  An id >= num_features (with 64-bit indices: ids >= 2^32
+ *  included) forms no address and ORs kCompactErrIndex into *error (a device
+ *  word the caller zeroed).  num_features in 1 .. kCompactMaxFeatures, nnz <
+ *  2^31.
+ */
+void LaunchCompactMark(const CsrView& csr, uint64_t base, uint64_t nnz, uint64_t num_features,
+                       void* scratch, uint32_t* error, hipStream_t stream);
+/*! \brief U2 + K3: the popcount of every bitmap word, scanned in place; *total
+ *  (a device u64) receives U, the number of distinct ids */
+void LaunchCompactCount(uint64_t num_features, void* scratch, uint64_t* total, hipStream_t stream);
+/*! \brief U3: the set bits as ids[0 .. U), strictly ascending; a position at
+ *  or past `capacity` (entries of ids) is not written */
+void LaunchCompactEmit(uint64_t num_features, const void* scratch, uint64_t capacity, int64_t* ids,
+                       hipStream_t stream);
+/*! \brief U4: slot[j] = position in ids of the id of entry base + j, j < nnz;
+ *  an id >= num_features (U1 flagged it) gets slot 0 */
+void LaunchCompactRemap(const CsrView& csr, uint64_t base, uint64_t nnz, uint64_t num_features,
+                        const void* scratch, int32_t* slot, hipStream_t stream);
+// ----------------- lazy optimizer step (optim_kernels.hip) -----------------
+/*! \brief update rules of L1 */
+enum LazyRule : int { kLazyAdagrad = 0, kLazyFtrl = 1 };
+/*! \brief hyper-parameters by position: adagrad (lr, eps, l2, -), ftrl (alpha, beta, l1, l2) */
+struct LazyHyper {
+  float a, b, c, d;
+};
+/*! \brief bit L1 ORs into its error word: a row id >= features or not strictly ascending */
+constexpr uint32_t kLazyErrIds = 1;
+/*!
+ * \brief L1: one optimizer step on rows ids[0 .. nrows) of param [features x
+ *  width] from grad [nrows x width] (ids == nullptr: rows 0 .. nrows - 1),
+ *  updating state0 (adagrad: n; ftrl: z) and state1 (ftrl: n; else unused,
+ *  may be null), all row-major contiguous f32 shaped as param.  The formulas:
+ *  optim_kernels.hip.  A row whose id is >= features or not strictly between
+ *  its neighbours' ids is skipped and ORs kLazyErrIds into *error (a device
+ *  word the caller zeroed); rows not named are neither read nor written.  No
+ *  atomics on the tensors.  nrows == 0 or width == 0 returns before any HIP
+ *  call.
+ */
+void LaunchLazyUpdate(int rule, float* param, const int64_t* ids, const float* grad, float* state0,
+                      float* state1, uint64_t features, uint64_t nrows, uint64_t width,
+                      const LazyHyper& hyper, uint32_t* error, hipStream_t stream);
 /*! \brief fill n floats with v */
 void LaunchFill(float* p, size_t n, float v, hipStream_t stream);
 /*!

@@ -1083,6 +1083,58 @@ PYBIND11_MODULE(_dmlc, m) {
   m.def("csr_gather_scratch_words", &gpu::CSRGatherScratchWords, py::arg("n_sel"));
   m.def("csr_gather_run_entries", &gpu::CSRGatherRunEntries);
   m.def(
+      "compact_mark",
+      [stream_of](const CsrArg& csr, uint64_t base, uint64_t nnz, uint64_t num_features,
+                  uintptr_t scratch, uintptr_t total, uintptr_t error, uintptr_t stream) {
+        // U1, U2 and the scan of the counts: *total becomes U
+        gpu::LaunchCompactMark(View(csr), base, nnz, num_features, Ptr<void>(scratch),
+                               Ptr<uint32_t>(error), stream_of(stream));
+        gpu::LaunchCompactCount(num_features, Ptr<void>(scratch), Ptr<uint64_t>(total),
+                                stream_of(stream));
+      },
+      py::arg("csr"), py::arg("base"), py::arg("nnz"), py::arg("num_features"),
+      py::arg("scratch"), py::arg("total"), py::arg("error"), py::arg("stream"));
+  m.def(
+      "compact_emit",
+      [stream_of](const CsrArg& csr, uint64_t base, uint64_t nnz, uint64_t num_features,
+                  uintptr_t scratch, uint64_t capacity, uintptr_t ids, uintptr_t slot,
+                  uintptr_t out_offset, uintptr_t stream) {
+        // U3, U4 and the batch's row pointer (K10: the slice's, rebased to 0)
+        const gpu::CsrView view = View(csr);
+        gpu::LaunchCompactEmit(num_features, Ptr<const void>(scratch), capacity, Ptr<int64_t>(ids),
+                               stream_of(stream));
+        gpu::LaunchCompactRemap(view, base, nnz, num_features, Ptr<const void>(scratch),
+                                Ptr<int32_t>(slot), stream_of(stream));
+        if (out_offset != 0) {
+          gpu::LaunchOffsetRebase(view.offset, view.nrows, base, 0, Ptr<uint64_t>(out_offset),
+                                  stream_of(stream));
+        }
+      },
+      py::arg("csr"), py::arg("base"), py::arg("nnz"), py::arg("num_features"),
+      py::arg("scratch"), py::arg("capacity"), py::arg("ids"), py::arg("slot"),
+      py::arg("out_offset"), py::arg("stream"));
+  m.def("compact_max_features", []() { return gpu::kCompactMaxFeatures; },
+        "largest num_features ops.compact_features takes");
+  m.def("compact_scratch_bytes", &gpu::CompactScratchBytes, py::arg("num_features"),
+        "bytes of 16-byte aligned scratch compact_mark / compact_emit share");
+  m.attr("compact_err_index") = gpu::kCompactErrIndex;
+  m.def(
+      "lazy_update",
+      [stream_of](int rule, uintptr_t param, uintptr_t ids, uintptr_t grad, uintptr_t state0,
+                  uintptr_t state1, uint64_t features, uint64_t nrows, uint64_t width, float a,
+                  float b, float c, float d, uintptr_t error, uintptr_t stream) {
+        gpu::LaunchLazyUpdate(rule, Ptr<float>(param), Ptr<const int64_t>(ids),
+                              Ptr<const float>(grad), Ptr<float>(state0), Ptr<float>(state1),
+                              features, nrows, width, gpu::LazyHyper{a, b, c, d},
+                              Ptr<uint32_t>(error), stream_of(stream));
+      },
+      py::arg("rule"), py::arg("param"), py::arg("ids"), py::arg("grad"), py::arg("state0"),
+      py::arg("state1"), py::arg("features"), py::arg("nrows"), py::arg("width"), py::arg("a"),
+      py::arg("b"), py::arg("c"), py::arg("d"), py::arg("error"), py::arg("stream"));
+  m.attr("lazy_adagrad") = static_cast<int>(gpu::kLazyAdagrad);
+  m.attr("lazy_ftrl") = static_cast<int>(gpu::kLazyFtrl);
+  m.attr("lazy_err_ids") = gpu::kLazyErrIds;
+  m.def(
       "hashed_dense",
       [stream_of](const CsrArg& csr, int dim, float scale, uint32_t seed, uintptr_t out, bool fp8,
                   uintptr_t stream) {
