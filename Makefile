@@ -34,7 +34,7 @@ CPU_SRCS := src/logging.cc src/fault.cc src/io.cc src/recordio.cc src/data.cc sr
   src/io/shard_reader.cc src/io/http.cc src/io/s3_filesys.cc src/io/azure_filesys.cc \
   src/io/hdfs_filesys.cc \
   src/gpu/runtime.cc src/gpu/chunk_feed.cc src/gpu/device_parser.cc src/gpu/device_recordio.cc src/gpu/device_row_iter.cc \
-  src/gpu/device_page_cache.cc src/gpu/text_pack.cc \
+  src/gpu/device_page_cache.cc src/gpu/text_pack.cc src/gpu/text_pack_dense.cc \
   src/dist/tracker_client.cc src/dist/communicator.cc
 HIP_SRCS := $(wildcard src/gpu/*.hip)
 
@@ -74,8 +74,9 @@ test-bin: $(BUILD)/dmlc_unittest
 
 # Sanitizer builds of the CPU library + unit tests: no HIP code,
 # so they run anywhere.  `make tsan && build/dmlc_unittest_tsan`.
-# (src/gpu/text_pack.cc is plain C++: its unit tests run under the sanitizers too)
-SAN_SRCS := $(filter-out src/gpu/% src/dist/communicator.cc,$(CPU_SRCS)) src/gpu/text_pack.cc
+# (src/gpu/text_pack.cc and text_pack_dense.cc are plain C++: its unit tests run under the sanitizers too)
+SAN_SRCS := $(filter-out src/gpu/% src/dist/communicator.cc,$(CPU_SRCS)) src/gpu/text_pack.cc \
+  src/gpu/text_pack_dense.cc
 SAN_FLAGS := -std=c++17 -O1 -g -fno-omit-frame-pointer -ffp-contract=off $(WARN) -Iinclude -Isrc \
   -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include -fopenmp
 $(BUILD)/dmlc_unittest_tsan: $(TEST_SRCS) $(SAN_SRCS) $(HEADERS)

@@ -21,7 +21,9 @@ write_synthetic = _dmlc.write_synthetic
 # packed H2D (src/gpu/text_pack.h): the host packer, its CPU reference unpack
 # and the device unpack kernel, for tests and measurements
 pack_text = _dmlc.pack_text
+pack_text_pool = _dmlc.pack_text_pool
 pack_isa_supported = _dmlc.pack_isa_supported
+pack_isa_supported_dense = _dmlc.pack_isa_supported_dense
 unpack_text_reference = _dmlc.unpack_text_reference
 unpack_text_device = _dmlc.unpack_text_device
 
@@ -94,7 +96,11 @@ class GPUParser:
     ``delimiter``.  ``packed_h2d`` ("auto" | 0 | 1): send chunks over PCIe as
     4-bit codes packed by ``read_threads`` host threads and expand them on the
     GPU (zero-copy source only; ``stats()`` reports ``packed_chunks``,
-    ``raw_chunks``, ``link_bytes``, ``head_packed``).  ``copy_streams`` (1 |
+    ``raw_chunks``, ``link_bytes``, ``head_packed``).  ``pack_code`` ("auto" |
+    "nibble" | "dense"): the code they are sent in; dense, with entries such
+    as ``:0.`` chosen per chunk, is the default from 1 MiB chunks and 16
+    ``read_threads`` on
+    (``dense_chunks``, ``escape_bytes``, ``raw_blocks``).  ``copy_streams`` (1 |
     2) and ``pack_head`` (0 | 1): see ``doc/gpu_ingestion.md``.  URI ``?k=v``
     arguments override them.
     """

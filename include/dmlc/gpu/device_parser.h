@@ -91,6 +91,16 @@ struct DeviceParserConfig {
    */
   int packed_h2d{-1};
   /*!
+   * \brief packed H2D, the code chunks cross the link in (`?pack_code=`):
+   *  0 nibble, 4 bits per text byte (src/gpu/text_pack.h); 1 dense, a 4-bit
+   *  code whose entries may be strings such as `:0.`, chosen per chunk from a
+   *  sample of its text (src/gpu/text_pack_dense.h); -1 auto: dense when
+   *  chunk_bytes >= 1 MiB (the threshold of packed_h2d=auto) and read_threads
+   *  >= 16 (its encoder is the slower one: with fewer threads the pool would
+   *  fall behind the link), nibble otherwise.
+   */
+  int pack_code{-1};
+  /*!
    * \brief packed H2D, test and measurement hook (not a tuning knob): the
    *  submitting thread waits for every chunk's pack
    *  instead of sending a chunk the pool has not started raw (`?pack_wait=1`).
@@ -160,7 +170,7 @@ struct DeviceParserConfig {
   int shuffle_seed{0};
   /*! \brief apply `?k=v` overrides (chunk_mb, pinned_slots, device_slots,
    *  read_threads, device, format, label_column, weight_column, delimiter,
-   *  fast_path, one_pass, prelaunch, zero_copy, packed_h2d, pack_wait, pack_head,
+   *  fast_path, one_pass, prelaunch, zero_copy, packed_h2d, pack_code, pack_wait, pack_head,
    *  copy_streams, zc_pin_budget_mb,
    *  zc_window_mb, hbm_cache, replay_chunk_mb, replay_first_mb,
    *  shuffle_parts, shuffle_seed) */
@@ -219,6 +229,9 @@ struct DeviceParserStats {
   /*! \brief packed H2D: chunks sent as 4-bit codes / sent raw, bytes that
    *  crossed the link, exception blocks sent with packed chunks */
   size_t packed_chunks{0}, raw_chunks{0}, link_bytes{0}, exception_blocks{0};
+  /*! \brief packed H2D, dense code: packed chunks sent in it, bytes they sent
+   *  through the escape code, blocks they stored raw */
+  size_t dense_chunks{0}, escape_bytes{0}, raw_blocks{0};
   /*! \brief packed H2D: passes whose first piece was packed before the pass
    *  began (cfg.pack_head) and was submitted packed */
   size_t head_packed{0};

@@ -15,6 +15,7 @@
 #include "../io/line_split.h"
 #include "./kernels.h"
 #include "./text_pack.h"
+#include "./text_pack_dense.h"
 
 namespace dmlc {
 namespace gpu {
@@ -334,7 +335,16 @@ void ChunkFeed::FillPipeline() {
       // arena's too) is whole even if the chunk is never parsed
       copied_[d]->Record(copy);
       DMLC_HIP_CHECK(hipStreamWaitEvent(unpack_->get(), copied_[d]->get(), 0));
-      LaunchUnpackText(dstage_[d]->get(), size, job->nexc, alphabet_, dst, unpack_->get());
+      if (job->dense) {
+        LaunchUnpackDense(dstage_[d]->get(), size,
+                          static_cast<uint32_t>(DenseRanges(size, pool_->range_blocks())),
+                          static_cast<uint32_t>(pool_->range_blocks()), dst, unpack_->get());
+        stats_->dense_chunks += 1;
+        stats_->escape_bytes += job->escape_bytes;
+        stats_->raw_blocks += job->raw_blocks;
+      } else {
+        LaunchUnpackText(dstage_[d]->get(), size, job->nexc, alphabet_, dst, unpack_->get());
+      }
       unpacked_[d]->Record(unpack_->get());
       pack_slot = job->slot;
       stats_->packed_chunks += 1;
@@ -364,7 +374,16 @@ void ChunkFeed::FillPipeline() {
 void ChunkFeed::StartPacking(bool csv_alphabet) {
   PackAlphabet(csv_alphabet, cfg_.delimiter, alphabet_);
   // the pool packs every queued piece, the one nearest the cursor first
-  pool_.reset(new PackPool(cfg_.read_threads, alphabet_, /*distance=*/0));
+  // auto: the dense encoder packs about 9 GB/s of text per thread inside the
+  // pool (EPYC 9575F) where the link takes 128 GB/s of it, and a pool that is
+  // slower than the link loses more than the code saves: measured with 4 and
+  // 8 threads, profiles/dense_pack/README.md
+  const bool dense = cfg_.pack_code == 1 ||
+                     (cfg_.pack_code < 0 && cfg_.chunk_bytes >= (size_t(1) << 20) &&
+                      cfg_.read_threads >= kDenseMinThreads);
+  pool_.reset(new PackPool(cfg_.read_threads, alphabet_, /*distance=*/0, PackPool::kRangeBlocks,
+                           dense ? PackCode::kDense : PackCode::kNibble, csv_alphabet,
+                           cfg_.delimiter));
   // a slot per lookahead entry and per packed chunk in flight
   pack_slots_ =
       std::vector<PinnedBuffer>(kPackLookahead + static_cast<size_t>(cfg_.device_slots) + 1);

@@ -213,6 +213,9 @@ class ChunkFeed {
   static constexpr size_t kPackLookahead = 4;
   static constexpr size_t kPackDistance = 2;
   static constexpr size_t kPackCaughtUp = 8;
+  /*! \brief pack_code=auto: pool threads from which the dense code
+   *  (text_pack_dense.h) is used; its encoder is the slower one */
+  static constexpr int kDenseMinThreads = 16;
   /*! \brief pieces of the next pass queued to the pool when a pass ends: the
    *  second is packed while the first crosses the link */
   static constexpr size_t kHeadJobs = 2;

@@ -102,6 +102,10 @@ void DeviceParserConfig::Update(const std::map<std::string, std::string>& args) 
       pack_head = v != "0" && v != "false";
     } else if (k == "copy_streams") {
       copy_streams = std::atoi(v.c_str());
+    } else if (k == "pack_code") {
+      CHECK(v == "auto" || v == "-1" || v == "nibble" || v == "dense")
+          << "pack_code must be auto, nibble or dense";
+      pack_code = v == "nibble" ? 0 : (v == "dense" ? 1 : -1);
     } else if (k == "packed_h2d") {
       packed_h2d = (v == "auto" || v == "-1") ? -1 : ((v == "0" || v == "false") ? 0 : 1);
     }

@@ -727,6 +727,13 @@ void LaunchFill(float* p, size_t n, float v, hipStream_t stream);
  */
 void LaunchUnpackText(const void* packed, size_t n, uint32_t nexc, const uint8_t alphabet[16],
                       char* dst, hipStream_t stream);
+/*!
+ * \brief the same for a dense chunk (text_pack_dense.h) of nranges ranges of
+ *  range_blocks blocks: table and directory are read from the chunk's header
+ *  on the device.  Exactly n bytes are written at dst (any alignment).
+ */
+void LaunchUnpackDense(const void* packed, size_t n, uint32_t nranges, uint32_t range_blocks,
+                       char* dst, hipStream_t stream);
 
 }  // namespace gpu
 }  // namespace dmlc

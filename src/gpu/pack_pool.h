@@ -17,7 +17,22 @@
  * The consumer queues jobs in file order (Push), and at submit time either
  * finds a job settled, claims a job the pool has not started (TryClaimRaw: the
  * piece goes over the link raw, the pool never touches it), or waits for the
- * pack in progress (Wait).  With a non-zero distance (SetDistance) the pool
+ * pack in progress (Wait).
+ *
+ * A pool of the dense code (text_pack_dense.h, PackCode::kDense) works the
+ * same way, but a range's packed size is not known beforehand: a thread packs
+ * its range into a buffer of its own, which stays in its cache, reserves that
+ * many bytes of the job's slot through an atomic cursor (ranges start at
+ * multiples of 16 bytes), copies the range there with streaming stores and
+ * fills the range's directory entry.  Ranges land in the order the threads
+ * finish them, so the packed bytes of a job depend on timing; the decoded
+ * text, the packed size and the set of per-range payloads do not.  The thread
+ * that reports the last range done writes the header (n, the table, the
+ * escape code, the directory).  There are no exception blocks and no copy
+ * phase.  The table of a job is chosen from a sample of its text when it is
+ * queued (Push, on the consumer's thread, ahead of the pool).
+ *
+ * With a non-zero distance (SetDistance) the pool
  * leaves jobs closer than that many pieces to the submit cursor unstarted, for
  * a consumer that claims them raw because the pool cannot keep up with the
  * link; with distance 0 it packs every job.
@@ -41,6 +56,7 @@
 #include <vector>
 
 #include "./text_pack.h"
+#include "./text_pack_dense.h"
 
 namespace dmlc {
 namespace gpu {
@@ -64,6 +80,11 @@ struct PackJob {
   // results, valid once state is kPacked
   size_t packed_bytes{0};
   uint32_t nexc{0};
+  /*! \brief dense code: the job's table (set by Push), and once packed whether
+   *  packed_bytes is a dense chunk, its escaped bytes and its raw blocks */
+  DenseTable table;
+  bool dense{false};
+  size_t escape_bytes{0}, raw_blocks{0};
   /*! \brief the piece's bytes were copied into the slot (its window goes away) */
   bool rescued{false};
   /*! \brief queued at the end of the previous pass for the start of this one
@@ -121,6 +142,9 @@ inline bool WaitMeansPoolBehind(bool link_idle, bool pack_wait, bool head_of_pas
   return link_idle && !pack_wait && !head_of_pass;
 }
 
+/*! \brief the code a pool packs with */
+enum class PackCode : int { kNibble = 0, kDense = 1 };
+
 class PackPool {
  public:
   /*! \brief blocks per range: 256 KiB of text */
@@ -128,11 +152,16 @@ class PackPool {
   /*! \brief exception blocks per range of the copy that follows the pack */
   static constexpr size_t kCopyBlocks = 1024;
 
+  /*! \param csv, delimiter the format, for the dense code's table */
   PackPool(int threads, const uint8_t alphabet[16], size_t distance,
-           size_t range_blocks = kRangeBlocks)
+           size_t range_blocks = kRangeBlocks, PackCode code = PackCode::kNibble,
+           bool csv = false, char delimiter = ',')
       : nthreads_(std::max(threads, 1)),
         distance_(distance),
         range_blocks_(std::max<size_t>(range_blocks, 1)),
+        code_(code),
+        csv_(csv),
+        delimiter_(delimiter),
         encoder_(alphabet) {
     std::memcpy(alphabet_, alphabet, 16);
     for (int t = 0; t < nthreads_; ++t) workers_.emplace_back([this]() { Work(); });
@@ -154,6 +183,10 @@ class PackPool {
   /*! \brief queue a job (file order); it must stay alive until it is settled
    *  (packed, rejected, claimed) or dropped by Quiesce */
   void Push(PackJob* job) {
+    if (code_ == PackCode::kDense) {
+      job->table = DenseSelectTable(reinterpret_cast<const uint8_t*>(job->ptr), job->size, csv_,
+                                    delimiter_);
+    }
     {
       std::lock_guard<std::mutex> lk(mu_);
       queue_.push_back(job);
@@ -199,6 +232,8 @@ class PackPool {
   }
   /*! \brief cumulative wall seconds during which at least one job was open */
   double pack_sec() const { return pack_sec_.load(std::memory_order_relaxed); }
+  PackCode code() const { return code_; }
+  size_t range_blocks() const { return range_blocks_; }
 
  private:
   /*! \brief a job being packed.  A thread may touch an Open (and its job) only
@@ -220,6 +255,12 @@ class PackPool {
     bool copying{false};
     int result{PackJob::kRejected};
     std::exception_ptr err;  // under mu_
+    // dense code: the slot's cursor and its bound, the directory, the job's
+    // encoder and its counters
+    std::atomic<size_t> cursor{0}, escape_bytes{0}, raw_blocks{0};
+    size_t limit{0};
+    std::vector<DenseDirEntry> dir;
+    std::unique_ptr<DenseEncoder> dense;
   };
   static constexpr int kOpenJobs = 2;
 
@@ -265,6 +306,18 @@ class PackPool {
       o->copying = false;
       o->result = PackJob::kRejected;
       try {
+        if (code_ == PackCode::kDense) {
+          const size_t nranges = DenseRanges(job->size, range_blocks_);
+          o->dense.reset(new DenseEncoder(job->table));
+          o->dir.assign(nranges, DenseDirEntry{0, 0});
+          o->cursor.store(DenseHeaderBytes(nranges, DenseEntryBytes(job->table)));
+          o->escape_bytes.store(0);
+          o->raw_blocks.store(0);
+          o->limit = job->ratio < 0
+                         ? DenseMaxBytes(job->size, range_blocks_)
+                         : static_cast<size_t>(job->ratio * static_cast<double>(job->size));
+          o->fits.store(true);
+        }
         DMLC_FAULT_POINT("pack");  // under mu_: the k-th pass is the k-th job
       } catch (...) {
         o->err = std::current_exception();
@@ -275,7 +328,27 @@ class PackPool {
     }
     return false;
   }
-  void RunRange(Open* o, size_t r) {
+  void RunRangeDense(Open* o, size_t r, uint8_t* scratch) {
+    const PackJob* job = o->job;
+    if (!o->fits.load(std::memory_order_relaxed)) return;
+    const size_t b0 = r * range_blocks_;
+    const size_t b1 = std::min(PackBlocks(job->size), b0 + range_blocks_);
+    if (b0 >= b1) return;  // (an empty job has one range and no block)
+    size_t escapes = 0, raw = 0;
+    const size_t len = PackRangeDense(reinterpret_cast<const uint8_t*>(job->ptr), job->size, b0,
+                                      b1, *o->dense, scratch, &escapes, &raw);
+    const size_t at = o->cursor.fetch_add(len);
+    if (at + len > o->limit) {
+      o->fits.store(false, std::memory_order_relaxed);
+      return;
+    }
+    DenseCopyOut(scratch, len, job->out + at);
+    o->dir[r] = DenseDirEntry{static_cast<uint32_t>(at), static_cast<uint32_t>(len)};
+    o->escape_bytes.fetch_add(escapes, std::memory_order_relaxed);
+    o->raw_blocks.fetch_add(raw, std::memory_order_relaxed);
+  }
+  void RunRange(Open* o, size_t r, uint8_t* scratch) {
+    if (code_ == PackCode::kDense) return RunRangeDense(o, r, scratch);
     const PackJob* job = o->job;
     const uint8_t* text = reinterpret_cast<const uint8_t*>(job->ptr);
     if (o->copying) {
@@ -301,6 +374,16 @@ class PackPool {
     PackJob* job = o->job;
     if (!o->fits.load()) return false;
     try {
+      if (code_ == PackCode::kDense) {
+        DenseWriteHeader(job->size, range_blocks_, job->table, o->dir, job->out);
+        job->packed_bytes = o->cursor.load();
+        job->nexc = 0;
+        job->dense = true;
+        job->escape_bytes = o->escape_bytes.load();
+        job->raw_blocks = o->raw_blocks.load();
+        o->result = PackJob::kPacked;
+        return false;
+      }
       o->all.clear();
       for (size_t r = 0; r < o->nranges; ++r) {
         o->all.insert(o->all.end(), o->exc[r].begin(), o->exc[r].end());
@@ -349,6 +432,11 @@ class PackPool {
     cv_work_.notify_all();  // a slot is free for the next queued job
   }
   void Work() {
+    // the dense code's range buffer, 64-byte aligned
+    std::vector<uint8_t> buffer(
+        code_ == PackCode::kDense ? DenseRangeCapacity(range_blocks_) + 64 : 0);
+    uint8_t* scratch =
+        buffer.data() + ((64 - (reinterpret_cast<uintptr_t>(buffer.data()) & 63)) & 63);
     for (;;) {
       Open* o = nullptr;
       size_t r = 0;
@@ -369,7 +457,7 @@ class PackPool {
       while (o != nullptr) {
         const size_t nranges = o->nranges;  // (of this phase: read while a range is held)
         try {
-          RunRange(o, r);
+          RunRange(o, r, scratch);
         } catch (...) {
           o->fits.store(false);
           std::lock_guard<std::mutex> lk(mu_);
@@ -395,6 +483,9 @@ class PackPool {
   const int nthreads_;
   std::atomic<size_t> distance_;
   const size_t range_blocks_;
+  const PackCode code_;
+  const bool csv_;
+  const char delimiter_;
   const PackEncoder encoder_;
   uint8_t alphabet_[16];
   std::mutex mu_;

@@ -32,7 +32,9 @@
 #include <vector>
 
 #include "../gpu/kernels.h"
+#include "../gpu/pack_pool.h"
 #include "../gpu/text_pack.h"
+#include "../gpu/text_pack_dense.h"
 #include "../io/http.h"
 #include "../io/line_split.h"
 #include "../io/recordio_split.h"
@@ -479,6 +481,9 @@ class PyDeviceParser {
     d["raw_chunks"] = s.raw_chunks;
     d["link_bytes"] = s.link_bytes;
     d["exception_blocks"] = s.exception_blocks;
+    d["dense_chunks"] = s.dense_chunks;
+    d["escape_bytes"] = s.escape_bytes;
+    d["raw_blocks"] = s.raw_blocks;
     d["head_packed"] = s.head_packed;
     d["pack_sec"] = s.pack_sec;
     d["wait_pack_sec"] = s.wait_pack_sec;
@@ -697,12 +702,29 @@ void BindRecordIO(py::module_& m) {
 }
 
 // ------------------------------------------------------------ packed H2D
-/*! \brief nibble-pack `text` (src/gpu/text_pack.h); None when the packed size
- *  exceeds ratio * len(text) (the chunk would cross the link raw) */
+/*! \brief pack `text` with the nibble code (src/gpu/text_pack.h) or the dense
+ *  code (text_pack_dense.h, its table chosen from the text, ranges of
+ *  range_blocks blocks); None when the packed size exceeds ratio * len(text)
+ *  (the chunk would cross the link raw) */
 py::object PackTextPy(const std::string& text, const std::string& format, const std::string& delimiter,
-                      double ratio, int isa) {
+                      double ratio, int isa, const std::string& code, size_t range_blocks) {
   CHECK(format == "libsvm" || format == "libfm" || format == "csv") << "unknown format " << format;
   CHECK_EQ(delimiter.size(), 1U) << "delimiter must be one character";
+  CHECK(code == "nibble" || code == "dense") << "unknown code " << code;
+  if (code == "dense") {
+    CHECK(gpu::PackIsaSupportedDense(static_cast<gpu::PackIsa>(isa)))
+        << "instruction set not supported";
+    CHECK_GE(range_blocks, 1U);
+    const uint8_t* bytes = reinterpret_cast<const uint8_t*>(text.data());
+    const gpu::DenseTable table =
+        gpu::DenseSelectTable(bytes, text.size(), format == "csv", delimiter[0]);
+    std::vector<uint8_t> packed;
+    if (!gpu::PackTextDense(bytes, text.size(), table, range_blocks, ratio, &packed,
+                            static_cast<gpu::PackIsa>(isa))) {
+      return py::none();
+    }
+    return py::bytes(reinterpret_cast<const char*>(packed.data()), packed.size());
+  }
   CHECK(gpu::PackIsaSupported(static_cast<gpu::PackIsa>(isa))) << "instruction set not supported";
   uint8_t alphabet[16];
   gpu::PackAlphabet(format == "csv", delimiter[0], alphabet);
@@ -714,7 +736,47 @@ py::object PackTextPy(const std::string& text, const std::string& format, const 
   return py::bytes(reinterpret_cast<const char*>(packed.data()), packed.size());
 }
 
+/*! \brief pack `text` through a PackPool of `threads` threads and ranges of
+ *  range_blocks blocks (test hook); None when it does not fit ratio */
+py::object PackTextPoolPy(const std::string& text, const std::string& format,
+                          const std::string& delimiter, size_t range_blocks, int threads,
+                          const std::string& code, double ratio) {
+  CHECK(format == "libsvm" || format == "libfm" || format == "csv") << "unknown format " << format;
+  CHECK_EQ(delimiter.size(), 1U) << "delimiter must be one character";
+  CHECK(code == "nibble" || code == "dense") << "unknown code " << code;
+  CHECK_GE(range_blocks, 1U);
+  uint8_t alphabet[16];
+  gpu::PackAlphabet(format == "csv", delimiter[0], alphabet);
+  const bool dense = code == "dense";
+  const size_t n = text.size();
+  // 64-byte aligned, as a pinned slot is
+  std::vector<uint8_t> out(
+      (dense ? gpu::DenseMaxBytes(n, range_blocks) : gpu::PackedBytes(n, gpu::PackBlocks(n))) + 128);
+  gpu::PackJob job;
+  job.ptr = text.data();
+  job.size = n;
+  job.ratio = ratio;
+  job.out = out.data() + ((64 - (reinterpret_cast<uintptr_t>(out.data()) & 63)) & 63);
+  {
+    py::gil_scoped_release release;
+    gpu::PackPool pool(threads, alphabet, /*distance=*/0, range_blocks,
+                       dense ? gpu::PackCode::kDense : gpu::PackCode::kNibble, format == "csv",
+                       delimiter[0]);
+    pool.Push(&job);
+    pool.Wait(&job);
+  }
+  if (job.state.load() != gpu::PackJob::kPacked) return py::none();
+  return py::bytes(reinterpret_cast<const char*>(job.out), job.packed_bytes);
+}
+
+bool IsDense(const std::string& packed) {
+  return gpu::IsDenseChunk(reinterpret_cast<const uint8_t*>(packed.data()), packed.size());
+}
+
 size_t CheckedPackedSize(const std::string& packed) {
+  if (IsDense(packed)) {
+    return gpu::DenseCheck(reinterpret_cast<const uint8_t*>(packed.data()), packed.size());
+  }
   CHECK_GE(packed.size(), sizeof(gpu::PackedHeader)) << "not a packed chunk";
   const gpu::PackedView v = gpu::ViewPacked(reinterpret_cast<const uint8_t*>(packed.data()));
   CHECK_EQ(v.bytes, packed.size()) << "packed chunk size mismatch";
@@ -729,6 +791,11 @@ size_t CheckedPackedSize(const std::string& packed) {
 /*! \brief CPU reference unpack */
 py::bytes UnpackTextReferencePy(const std::string& packed) {
   std::string out(CheckedPackedSize(packed), '\0');
+  if (IsDense(packed)) {
+    gpu::UnpackDenseReference(reinterpret_cast<const uint8_t*>(packed.data()),
+                              reinterpret_cast<uint8_t*>(&out[0]));
+    return py::bytes(out);
+  }
   gpu::UnpackReference(reinterpret_cast<const uint8_t*>(packed.data()),
                        reinterpret_cast<uint8_t*>(&out[0]));
   return py::bytes(out);
@@ -738,14 +805,26 @@ py::bytes UnpackTextReferencePy(const std::string& packed) {
  *  `fill`, at byte dst_offset; returns the whole buffer */
 py::bytes UnpackTextDevicePy(const std::string& packed, size_t dst_offset, size_t pad, int fill) {
   const size_t n = CheckedPackedSize(packed);
-  const gpu::PackedView v = gpu::ViewPacked(reinterpret_cast<const uint8_t*>(packed.data()));
+  const bool dense = IsDense(packed);
+  gpu::PackedView v;
+  gpu::DenseHeader dh;
+  if (dense) {
+    std::memcpy(&dh, packed.data(), sizeof(dh));
+  } else {
+    v = gpu::ViewPacked(reinterpret_cast<const uint8_t*>(packed.data()));
+  }
   gpu::DeviceBuffer src(packed.size()), dst(dst_offset + n + pad);
   gpu::Stream stream;
   DMLC_HIP_CHECK(hipMemcpyAsync(src.get(), packed.data(), packed.size(), hipMemcpyHostToDevice,
                                 stream.get()));
   DMLC_HIP_CHECK(hipMemsetAsync(dst.get(), fill, dst_offset + n + pad, stream.get()));
-  gpu::LaunchUnpackText(src.get(), n, v.header.nexc, v.header.alphabet,
-                        dst.get<char>() + dst_offset, stream.get());
+  if (dense) {
+    gpu::LaunchUnpackDense(src.get(), n, dh.nranges, dh.range_blocks,
+                           dst.get<char>() + dst_offset, stream.get());
+  } else {
+    gpu::LaunchUnpackText(src.get(), n, v.header.nexc, v.header.alphabet,
+                          dst.get<char>() + dst_offset, stream.get());
+  }
   DMLC_HIP_CHECK(hipGetLastError());
   std::string out(dst_offset + n + pad, '\0');
   DMLC_HIP_CHECK(hipMemcpyAsync(&out[0], dst.get(), out.size(), hipMemcpyDeviceToHost, stream.get()));
@@ -777,7 +856,13 @@ PYBIND11_MODULE(_dmlc, m) {
   m.doc() = "dmlc-core for MI355X: native runtime bindings";
   py::register_exception<dmlc::Error>(m, "DMLCError");
   m.def("pack_text", &PackTextPy, py::arg("text"), py::arg("format") = "libsvm",
-        py::arg("delimiter") = ",", py::arg("ratio") = gpu::kPackMaxRatio, py::arg("isa") = 0);
+        py::arg("delimiter") = ",", py::arg("ratio") = gpu::kPackMaxRatio, py::arg("isa") = 0,
+        py::arg("code") = "nibble", py::arg("range_blocks") = gpu::PackPool::kRangeBlocks);
+  m.def("pack_text_pool", &PackTextPoolPy, py::arg("text"), py::arg("format") = "libsvm",
+        py::arg("delimiter") = ",", py::arg("range_blocks") = gpu::PackPool::kRangeBlocks,
+        py::arg("threads") = 4, py::arg("code") = "dense", py::arg("ratio") = -1.0);
+  m.def("pack_isa_supported_dense",
+        [](int isa) { return gpu::PackIsaSupportedDense(static_cast<gpu::PackIsa>(isa)); });
   m.def("pack_isa_supported",
         [](int isa) { return gpu::PackIsaSupported(static_cast<gpu::PackIsa>(isa)); });
   m.def("unpack_text_reference", &UnpackTextReferencePy, py::arg("packed"));
