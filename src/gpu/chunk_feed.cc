@@ -15,6 +15,7 @@
 #include "../io/line_split.h"
 #include "./kernels.h"
 #include "./text_pack.h"
+#include "./text_pack_codec.h"
 #include "./text_pack_dense.h"
 
 namespace dmlc {
@@ -381,9 +382,10 @@ void ChunkFeed::StartPacking(bool csv_alphabet) {
   const bool dense = cfg_.pack_code == 1 ||
                      (cfg_.pack_code < 0 && cfg_.chunk_bytes >= (size_t(1) << 20) &&
                       cfg_.read_threads >= kDenseMinThreads);
-  pool_.reset(new PackPool(cfg_.read_threads, alphabet_, /*distance=*/0, PackPool::kRangeBlocks,
-                           dense ? PackCode::kDense : PackCode::kNibble, csv_alphabet,
-                           cfg_.delimiter));
+  pool_.reset(new PackPool(cfg_.read_threads,
+                           MakePackCodec(dense ? PackCode::kDense : PackCode::kNibble,
+                                         csv_alphabet, cfg_.delimiter),
+                           /*distance=*/0));
   // a slot per lookahead entry and per packed chunk in flight
   pack_slots_ =
       std::vector<PinnedBuffer>(kPackLookahead + static_cast<size_t>(cfg_.device_slots) + 1);

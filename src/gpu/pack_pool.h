@@ -1,36 +1,25 @@
 /*!
  * \file src/gpu/pack_pool.h
- * \brief Thread pool that nibble-packs upcoming text pieces (text_pack.h) into
- *  pinned slots ahead of the H2D submit cursor, and the rule by which the
- *  submit loop sends a piece packed or raw (DecideSubmit).
+ * \brief Thread pool that packs upcoming text pieces into pinned slots ahead
+ *  of the H2D submit cursor, and the rule by which the submit loop sends a
+ *  piece packed or raw (DecideSubmit).  The pool is the scheduler only: the
+ *  code it packs with is a PackCodec (pack_codec.h; the text codes are in
+ *  text_pack_codec.h).
  *
  * The pool packs the queue front.  A job is cut into ranges of `range_blocks`
  * 256-byte blocks which the threads claim with an atomic cursor; a thread that
  * finds no range left in an open job moves straight on to the next queued one
- * (two jobs are open at most), and the thread that reports a job's last range
- * done writes its header and exception indices and settles it; a long list of
- * exception blocks is copied in ranges claimed the same way first.  No thread
- * waits for another.  The exception lists are kept per range and
- * concatenated in range order, so a job's packed bytes equal PackText of the
- * same input whatever the thread count or the timing.
+ * (two jobs are open at most).  The thread that reports the last range done
+ * ends the phase (PackJobState::Finish): the job is then settled, or the codec
+ * names the ranges of a further phase, which are claimed the same way, the
+ * first of them by that thread.  No thread waits for another.  A job that does
+ * not fit, or whose codec throws, does no further work: it is settled rejected
+ * or failed, and Wait rethrows what was thrown.
  *
  * The consumer queues jobs in file order (Push), and at submit time either
  * finds a job settled, claims a job the pool has not started (TryClaimRaw: the
  * piece goes over the link raw, the pool never touches it), or waits for the
  * pack in progress (Wait).
- *
- * A pool of the dense code (text_pack_dense.h, PackCode::kDense) works the
- * same way, but a range's packed size is not known beforehand: a thread packs
- * its range into a buffer of its own, which stays in its cache, reserves that
- * many bytes of the job's slot through an atomic cursor (ranges start at
- * multiples of 16 bytes), copies the range there with streaming stores and
- * fills the range's directory entry.  Ranges land in the order the threads
- * finish them, so the packed bytes of a job depend on timing; the decoded
- * text, the packed size and the set of per-range payloads do not.  The thread
- * that reports the last range done writes the header (n, the table, the
- * escape code, the directory).  There are no exception blocks and no copy
- * phase.  The table of a job is chosen from a sample of its text when it is
- * queued (Push, on the consumer's thread, ahead of the pool).
  *
  * With a non-zero distance (SetDistance) the pool
  * leaves jobs closer than that many pieces to the submit cursor unstarted, for
@@ -47,16 +36,17 @@
 #include <algorithm>
 #include <atomic>
 #include <condition_variable>
-#include <cstring>
 #include <deque>
 #include <exception>
 #include <memory>
 #include <mutex>
 #include <thread>
+#include <utility>
 #include <vector>
 
-#include "./text_pack.h"
-#include "./text_pack_dense.h"
+#include "./pack_codec.h"
+#include "./text_pack.h"        // kPackMaxRatio
+#include "./text_pack_dense.h"  // PackJob::table
 
 namespace dmlc {
 namespace gpu {
@@ -142,28 +132,19 @@ inline bool WaitMeansPoolBehind(bool link_idle, bool pack_wait, bool head_of_pas
   return link_idle && !pack_wait && !head_of_pass;
 }
 
-/*! \brief the code a pool packs with */
-enum class PackCode : int { kNibble = 0, kDense = 1 };
-
 class PackPool {
  public:
   /*! \brief blocks per range: 256 KiB of text */
   static constexpr size_t kRangeBlocks = 1024;
-  /*! \brief exception blocks per range of the copy that follows the pack */
-  static constexpr size_t kCopyBlocks = 1024;
 
-  /*! \param csv, delimiter the format, for the dense code's table */
-  PackPool(int threads, const uint8_t alphabet[16], size_t distance,
-           size_t range_blocks = kRangeBlocks, PackCode code = PackCode::kNibble,
-           bool csv = false, char delimiter = ',')
+  /*! \param codec the code the pool packs with */
+  PackPool(int threads, std::unique_ptr<PackCodec> codec, size_t distance,
+           size_t range_blocks = kRangeBlocks)
       : nthreads_(std::max(threads, 1)),
         distance_(distance),
         range_blocks_(std::max<size_t>(range_blocks, 1)),
-        code_(code),
-        csv_(csv),
-        delimiter_(delimiter),
-        encoder_(alphabet) {
-    std::memcpy(alphabet_, alphabet, 16);
+        codec_(std::move(codec)) {
+    for (Open& o : open_) o.state = codec_->NewState();
     for (int t = 0; t < nthreads_; ++t) workers_.emplace_back([this]() { Work(); });
   }
   ~PackPool() {
@@ -183,10 +164,7 @@ class PackPool {
   /*! \brief queue a job (file order); it must stay alive until it is settled
    *  (packed, rejected, claimed) or dropped by Quiesce */
   void Push(PackJob* job) {
-    if (code_ == PackCode::kDense) {
-      job->table = DenseSelectTable(reinterpret_cast<const uint8_t*>(job->ptr), job->size, csv_,
-                                    delimiter_);
-    }
+    codec_->Prepare(job);
     {
       std::lock_guard<std::mutex> lk(mu_);
       queue_.push_back(job);
@@ -232,7 +210,6 @@ class PackPool {
   }
   /*! \brief cumulative wall seconds during which at least one job was open */
   double pack_sec() const { return pack_sec_.load(std::memory_order_relaxed); }
-  PackCode code() const { return code_; }
   size_t range_blocks() const { return range_blocks_; }
 
  private:
@@ -241,26 +218,18 @@ class PackPool {
    *  job is settled, and the Open reused, only after every range is reported */
   struct Open {
     PackJob* job{nullptr};
+    /*! \brief the codec's side of the job (made once, reused job after job) */
+    std::unique_ptr<PackJobState> state;
+    /*! \brief the phase the ranges belong to and their count: changed under
+     *  mu_ by the thread that ends a phase */
+    int phase{0};
     size_t nranges{0};
     /*! \brief order of opening: the older job's ranges are claimed first */
     size_t order{0};
-    long exc_limit{0};
     std::atomic<size_t> next{0}, done{0};
-    std::atomic<long> exc_total{0};
     std::atomic<bool> fits{true};
-    /*! \brief exception blocks per range (entries keep their capacity) */
-    std::vector<std::vector<uint32_t>> exc;
-    std::vector<uint32_t> all;
-    /*! \brief the ranges are now those of the exception blocks' copy */
-    bool copying{false};
     int result{PackJob::kRejected};
     std::exception_ptr err;  // under mu_
-    // dense code: the slot's cursor and its bound, the directory, the job's
-    // encoder and its counters
-    std::atomic<size_t> cursor{0}, escape_bytes{0}, raw_blocks{0};
-    size_t limit{0};
-    std::vector<DenseDirEntry> dir;
-    std::unique_ptr<DenseEncoder> dense;
   };
   static constexpr int kOpenJobs = 2;
 
@@ -294,30 +263,17 @@ class PackPool {
       int expect = PackJob::kQueued;
       if (!job->state.compare_exchange_strong(expect, PackJob::kPacking)) continue;
       o->job = job;
-      o->nranges = std::max<size_t>(1, (PackBlocks(job->size) + range_blocks_ - 1) / range_blocks_);
+      o->phase = 0;
+      o->nranges = 1;  // (should Begin throw: one range, which does nothing)
       o->order = ++opened_;
-      o->exc_limit = PackMaxExceptions(job->size, job->ratio);
       o->next.store(0);
       o->done.store(0);
-      o->exc_total.store(0);
-      o->fits.store(o->exc_limit >= 0);
-      if (o->exc.size() < o->nranges) o->exc.resize(o->nranges);
       o->err = nullptr;
-      o->copying = false;
       o->result = PackJob::kRejected;
       try {
-        if (code_ == PackCode::kDense) {
-          const size_t nranges = DenseRanges(job->size, range_blocks_);
-          o->dense.reset(new DenseEncoder(job->table));
-          o->dir.assign(nranges, DenseDirEntry{0, 0});
-          o->cursor.store(DenseHeaderBytes(nranges, DenseEntryBytes(job->table)));
-          o->escape_bytes.store(0);
-          o->raw_blocks.store(0);
-          o->limit = job->ratio < 0
-                         ? DenseMaxBytes(job->size, range_blocks_)
-                         : static_cast<size_t>(job->ratio * static_cast<double>(job->size));
-          o->fits.store(true);
-        }
+        bool fits = true;
+        o->nranges = o->state->Begin(job, range_blocks_, &fits);
+        o->fits.store(fits);
         DMLC_FAULT_POINT("pack");  // under mu_: the k-th pass is the k-th job
       } catch (...) {
         o->err = std::current_exception();
@@ -328,80 +284,22 @@ class PackPool {
     }
     return false;
   }
-  void RunRangeDense(Open* o, size_t r, uint8_t* scratch) {
-    const PackJob* job = o->job;
-    if (!o->fits.load(std::memory_order_relaxed)) return;
-    const size_t b0 = r * range_blocks_;
-    const size_t b1 = std::min(PackBlocks(job->size), b0 + range_blocks_);
-    if (b0 >= b1) return;  // (an empty job has one range and no block)
-    size_t escapes = 0, raw = 0;
-    const size_t len = PackRangeDense(reinterpret_cast<const uint8_t*>(job->ptr), job->size, b0,
-                                      b1, *o->dense, scratch, &escapes, &raw);
-    const size_t at = o->cursor.fetch_add(len);
-    if (at + len > o->limit) {
-      o->fits.store(false, std::memory_order_relaxed);
-      return;
-    }
-    DenseCopyOut(scratch, len, job->out + at);
-    o->dir[r] = DenseDirEntry{static_cast<uint32_t>(at), static_cast<uint32_t>(len)};
-    o->escape_bytes.fetch_add(escapes, std::memory_order_relaxed);
-    o->raw_blocks.fetch_add(raw, std::memory_order_relaxed);
-  }
-  void RunRange(Open* o, size_t r, uint8_t* scratch) {
-    if (code_ == PackCode::kDense) return RunRangeDense(o, r, scratch);
-    const PackJob* job = o->job;
-    const uint8_t* text = reinterpret_cast<const uint8_t*>(job->ptr);
-    if (o->copying) {
-      PackCopyExceptions(text, job->size, o->all, r * kCopyBlocks,
-                         std::min(o->all.size(), (r + 1) * kCopyBlocks), job->out);
-      return;
-    }
-    std::vector<uint32_t>& exc = o->exc[r];
-    exc.clear();
-    if (!o->fits.load(std::memory_order_relaxed)) return;
-    const size_t b0 = r * range_blocks_;
-    const size_t b1 = std::min(PackBlocks(job->size), b0 + range_blocks_);
-    if (!PackRange(text, job->size, b0, b1, encoder_, job->out + sizeof(PackedHeader), &exc,
-                   &o->exc_total, o->exc_limit)) {
-      o->fits.store(false, std::memory_order_relaxed);
-    }
-  }
-  /*! \brief every range of the pack is reported and this thread alone holds
-   *  the job: write the header and the exception indices.  true: the copy of
-   *  the exception blocks is opened as ranges of its own and the caller holds
-   *  the first; false: the job is ready to be settled (o->result) */
-  bool FinishPack(Open* o) {
-    PackJob* job = o->job;
+  /*! \brief every range of the phase is reported and this thread alone holds
+   *  the job: end the phase.  true: a further phase is opened and the caller
+   *  holds its range 0; false: the job is ready to be settled (o->result) */
+  bool FinishPhase(Open* o) {
     if (!o->fits.load()) return false;
     try {
-      if (code_ == PackCode::kDense) {
-        DenseWriteHeader(job->size, range_blocks_, job->table, o->dir, job->out);
-        job->packed_bytes = o->cursor.load();
-        job->nexc = 0;
-        job->dense = true;
-        job->escape_bytes = o->escape_bytes.load();
-        job->raw_blocks = o->raw_blocks.load();
-        o->result = PackJob::kPacked;
-        return false;
-      }
-      o->all.clear();
-      for (size_t r = 0; r < o->nranges; ++r) {
-        o->all.insert(o->all.end(), o->exc[r].begin(), o->exc[r].end());
-      }
-      if (static_cast<long>(o->all.size()) > o->exc_limit) return false;
-      job->packed_bytes = PackFinishHeader(job->size, alphabet_, o->all, job->out);
-      job->nexc = static_cast<uint32_t>(o->all.size());
-      o->result = PackJob::kPacked;
-      const size_t ncopy = (o->all.size() + kCopyBlocks - 1) / kCopyBlocks;
-      if (ncopy <= 1) {
-        PackCopyExceptions(reinterpret_cast<const uint8_t*>(job->ptr), job->size, o->all, 0,
-                           o->all.size(), job->out);
+      bool packed = false;
+      const size_t nranges = o->state->Finish(o->phase, &packed);
+      if (nranges == 0) {
+        if (packed) o->result = PackJob::kPacked;
         return false;
       }
       {
         std::lock_guard<std::mutex> lk(mu_);
-        o->copying = true;
-        o->nranges = ncopy;
+        ++o->phase;
+        o->nranges = nranges;
         o->done.store(0);
         o->next.store(1);  // range 0 is the caller's
       }
@@ -432,9 +330,9 @@ class PackPool {
     cv_work_.notify_all();  // a slot is free for the next queued job
   }
   void Work() {
-    // the dense code's range buffer, 64-byte aligned
-    std::vector<uint8_t> buffer(
-        code_ == PackCode::kDense ? DenseRangeCapacity(range_blocks_) + 64 : 0);
+    // the codec's scratch buffer of this thread, 64-byte aligned
+    const size_t scratch_bytes = codec_->ScratchBytes(range_blocks_);
+    std::vector<uint8_t> buffer(scratch_bytes != 0 ? scratch_bytes + 64 : 0);
     uint8_t* scratch =
         buffer.data() + ((64 - (reinterpret_cast<uintptr_t>(buffer.data()) & 63)) & 63);
     for (;;) {
@@ -455,9 +353,14 @@ class PackPool {
       // range after range of this job; the next one is claimed before this
       // one is reported, so the job stays open in between
       while (o != nullptr) {
-        const size_t nranges = o->nranges;  // (of this phase: read while a range is held)
+        // (the phase and its ranges: read while a range is held)
+        const int phase = o->phase;
+        const size_t nranges = o->nranges;
         try {
-          RunRange(o, r, scratch);
+          // "does not fit" is sticky: the job's remaining ranges do no work
+          if (o->fits.load(std::memory_order_relaxed) && !o->state->Run(phase, r, scratch)) {
+            o->fits.store(false, std::memory_order_relaxed);
+          }
         } catch (...) {
           o->fits.store(false);
           std::lock_guard<std::mutex> lk(mu_);
@@ -465,7 +368,7 @@ class PackPool {
         }
         const size_t next = o->next.fetch_add(1);
         if (o->done.fetch_add(1) + 1 == nranges) {
-          if (!o->copying && FinishPack(o)) {
+          if (FinishPhase(o)) {
             r = 0;
           } else {
             Settle(o);
@@ -483,11 +386,7 @@ class PackPool {
   const int nthreads_;
   std::atomic<size_t> distance_;
   const size_t range_blocks_;
-  const PackCode code_;
-  const bool csv_;
-  const char delimiter_;
-  const PackEncoder encoder_;
-  uint8_t alphabet_[16];
+  const std::unique_ptr<PackCodec> codec_;
   std::mutex mu_;
   std::condition_variable cv_work_, cv_done_;
   std::deque<PackJob*> queue_;

@@ -34,6 +34,7 @@
 #include "../gpu/kernels.h"
 #include "../gpu/pack_pool.h"
 #include "../gpu/text_pack.h"
+#include "../gpu/text_pack_codec.h"
 #include "../gpu/text_pack_dense.h"
 #include "../io/http.h"
 #include "../io/line_split.h"
@@ -745,8 +746,6 @@ py::object PackTextPoolPy(const std::string& text, const std::string& format,
   CHECK_EQ(delimiter.size(), 1U) << "delimiter must be one character";
   CHECK(code == "nibble" || code == "dense") << "unknown code " << code;
   CHECK_GE(range_blocks, 1U);
-  uint8_t alphabet[16];
-  gpu::PackAlphabet(format == "csv", delimiter[0], alphabet);
   const bool dense = code == "dense";
   const size_t n = text.size();
   // 64-byte aligned, as a pinned slot is
@@ -759,9 +758,10 @@ py::object PackTextPoolPy(const std::string& text, const std::string& format,
   job.out = out.data() + ((64 - (reinterpret_cast<uintptr_t>(out.data()) & 63)) & 63);
   {
     py::gil_scoped_release release;
-    gpu::PackPool pool(threads, alphabet, /*distance=*/0, range_blocks,
-                       dense ? gpu::PackCode::kDense : gpu::PackCode::kNibble, format == "csv",
-                       delimiter[0]);
+    gpu::PackPool pool(threads,
+                       gpu::MakePackCodec(dense ? gpu::PackCode::kDense : gpu::PackCode::kNibble,
+                                          format == "csv", delimiter[0]),
+                       /*distance=*/0, range_blocks);
     pool.Push(&job);
     pool.Wait(&job);
   }

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../src/gpu/pack_pool.h"
+#include "../../src/gpu/text_pack_codec.h"
 #include "./testing.h"
 
 namespace {
@@ -77,7 +78,7 @@ TEST(PackHead, AdoptedHeadJobsEqualPackText) {
   // distance 2, as while the pool is behind the link: head jobs carry the
   // sequence numbers 0 and 1, so the cursor has to restart with them
   for (size_t distance : {size_t(0), size_t(2)}) {
-    PackPool pool(4, alphabet, distance);
+    PackPool pool(4, std::make_unique<dmlc::gpu::NibbleCodec>(alphabet), distance);
     pool.SetDistance(0);
     RunPass(&pool, 6, 300000);
     pool.SetDistance(distance);
@@ -117,7 +118,7 @@ TEST(PackHead, QuiesceLeavesNoHeadJobReferenced) {
   uint8_t alphabet[16];
   dmlc::gpu::PackAlphabet(false, ',', alphabet);
   for (int round = 0; round < 8; ++round) {
-    PackPool pool(4, alphabet, 0);
+    PackPool pool(4, std::make_unique<dmlc::gpu::NibbleCodec>(alphabet), 0);
     RunPass(&pool, 3, 100000);
     pool.SetSubmitted(0);
     std::vector<Piece> head;
@@ -145,7 +146,7 @@ TEST(PackHead, DestroyedWithHeadJobsOpen) {
   head.push_back(MakePiece(1 << 20, 5, 0, true));
   head.push_back(MakePiece(1 << 20, 6, 1, true));
   {
-    PackPool pool(4, alphabet, 0);
+    PackPool pool(4, std::make_unique<dmlc::gpu::NibbleCodec>(alphabet), 0);
     RunPass(&pool, 2, 100000);
     pool.SetSubmitted(0);
     for (auto& p : head) pool.Push(p.job.get());

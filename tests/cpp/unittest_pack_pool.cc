@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../src/gpu/pack_pool.h"
+#include "../../src/gpu/text_pack_codec.h"
 #include "./testing.h"
 
 namespace {
@@ -72,7 +73,7 @@ TEST(PackPool, EveryJobWaitedFor) {
   // 1 MiB pieces: all four threads take a part; every 40th block of the odd
   // pieces is an exception (inside the 3/4 rule)
   std::vector<Piece> pieces = MakePieces(6, 1 << 20, 40);
-  PackPool pool(4, alphabet, /*distance=*/0);
+  PackPool pool(4, std::make_unique<dmlc::gpu::NibbleCodec>(alphabet), /*distance=*/0);
   for (auto& p : pieces) pool.Push(p.job.get());
   for (size_t i = 0; i < pieces.size(); ++i) {
     // the submit cursor passes a job before its pack has started: with
@@ -89,7 +90,7 @@ TEST(PackPool, RejectedWhenMostlyExceptions) {
   uint8_t alphabet[16];
   dmlc::gpu::PackAlphabet(false, ',', alphabet);
   std::vector<Piece> pieces = MakePieces(4, 300000, 1);  // odd pieces: every block
-  PackPool pool(3, alphabet, 0);
+  PackPool pool(3, std::make_unique<dmlc::gpu::NibbleCodec>(alphabet), 0);
   for (auto& p : pieces) pool.Push(p.job.get());
   for (size_t i = 0; i < pieces.size(); ++i) {
     pool.Wait(pieces[i].job.get());
@@ -106,7 +107,7 @@ TEST(PackPool, HybridSubmitLoop) {
   dmlc::gpu::PackAlphabet(false, ',', alphabet);
   const size_t kLookahead = 4, kDistance = 2;
   std::vector<Piece> pieces = MakePieces(40, 70000);
-  PackPool pool(4, alphabet, kDistance);
+  PackPool pool(4, std::make_unique<dmlc::gpu::NibbleCodec>(alphabet), kDistance);
   size_t pushed = 0, packed = 0, raw = 0;
   for (size_t submitted = 0; submitted < pieces.size();) {
     // as DeviceParserImpl::NextPackJob: fill the lookahead, pop the front
@@ -136,7 +137,7 @@ TEST(PackPool, PoolThreadErrorSurfacesInWait) {
   uint8_t alphabet[16];
   dmlc::gpu::PackAlphabet(false, ',', alphabet);
   std::vector<Piece> pieces = MakePieces(5, 65536);
-  PackPool pool(4, alphabet, 0);
+  PackPool pool(4, std::make_unique<dmlc::gpu::NibbleCodec>(alphabet), 0);
   dmlc::fault::Configure("pack:2");
   for (auto& p : pieces) pool.Push(p.job.get());
   pool.SetSubmitted(pieces.size());
@@ -159,7 +160,7 @@ TEST(PackPool, QuiesceDropsQueuedJobs) {
   dmlc::gpu::PackAlphabet(false, ',', alphabet);
   for (int round = 0; round < 5; ++round) {
     std::vector<Piece> pieces = MakePieces(8, 200000);
-    PackPool pool(4, alphabet, 0);
+    PackPool pool(4, std::make_unique<dmlc::gpu::NibbleCodec>(alphabet), 0);
     for (auto& p : pieces) pool.Push(p.job.get());
     pool.Wait(pieces[0].job.get());
     pool.Quiesce();

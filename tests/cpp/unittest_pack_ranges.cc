@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../src/gpu/pack_pool.h"
+#include "../../src/gpu/text_pack_codec.h"
 #include "./testing.h"
 
 namespace {
@@ -97,7 +98,7 @@ TEST(PackRanges, OutputEqualsPackText) {
   const size_t sizes[] = {1,      255,        256,          257, kRange - kBlock,
                           kRange, kRange + 1, 3 * kRange + 777};
   for (int threads : {1, 3, 16}) {  // 16: more threads than any of these has ranges
-    PackPool pool(threads, alphabet, 0);
+    PackPool pool(threads, std::make_unique<dmlc::gpu::NibbleCodec>(alphabet), 0);
     std::vector<Piece> pieces;
     for (size_t n : sizes) {
       // 0: none; 1: a few; 2: every block, whose copy is shared in ranges too
@@ -143,7 +144,7 @@ TEST(PackRanges, SmallJobsBetweenLargeOnes) {
     if (i % 5 == 0) Spoil(&pieces[i].text, 3);
     MakeJob(&pieces[i], i, -1.0);
   }
-  PackPool pool(4, alphabet, 0);
+  PackPool pool(4, std::make_unique<dmlc::gpu::NibbleCodec>(alphabet), 0);
   for (auto& p : pieces) pool.Push(p.job.get());
   for (auto& p : pieces) {
     pool.Wait(p.job.get());
@@ -164,7 +165,7 @@ TEST(PackRanges, RejectedInALateRange) {
   ASSERT_GT(static_cast<long>(blocks - 2 * PackPool::kRangeBlocks),
             dmlc::gpu::PackMaxExceptions(pieces[1].text.size()));
   for (size_t i = 0; i < pieces.size(); ++i) MakeJob(&pieces[i], i, dmlc::gpu::kPackMaxRatio);
-  PackPool pool(3, alphabet, 0);
+  PackPool pool(3, std::make_unique<dmlc::gpu::NibbleCodec>(alphabet), 0);
   for (auto& p : pieces) pool.Push(p.job.get());
   for (auto& p : pieces) pool.Wait(p.job.get());
   ExpectEqualsPackText(pieces[0], alphabet);
@@ -180,7 +181,7 @@ TEST(PackRanges, RejectedInALateRange) {
 TEST(PackRanges, QuiesceWhileTwoJobsAreOpen) {
   uint8_t alphabet[16];
   dmlc::gpu::PackAlphabet(false, ',', alphabet);
-  PackPool pool(4, alphabet, 0);
+  PackPool pool(4, std::make_unique<dmlc::gpu::NibbleCodec>(alphabet), 0);
   for (int round = 0; round < 8; ++round) {
     // three ranges each and four threads: when the first job is settled, the
     // next two are open
@@ -212,7 +213,7 @@ TEST(PackRanges, ClaimRawRacesThePool) {
   }
   size_t claimed = 0, packed = 0;
   {
-    PackPool pool(4, alphabet, 0);
+    PackPool pool(4, std::make_unique<dmlc::gpu::NibbleCodec>(alphabet), 0);
     for (auto& p : pieces) pool.Push(p.job.get());
     // from the back, where the pool arrives last
     for (size_t i = pieces.size(); i-- > 0;) {
@@ -289,7 +290,7 @@ TEST(PackRanges, SubmitLoopWithABusyLink) {
     pieces[i].text = Text(kRange + 5000 + 13 * i, static_cast<unsigned>(i));
     MakeJob(&pieces[i], i, -1.0);
   }
-  PackPool pool(4, alphabet, 0);
+  PackPool pool(4, std::make_unique<dmlc::gpu::NibbleCodec>(alphabet), 0);
   size_t pushed = 0, raw = 0, packed = 0, inflight = 0;
   const auto link_busy = [&inflight]() { return inflight != 0; };
   for (size_t submitted = 0; submitted < pieces.size();) {

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../src/gpu/pack_pool.h"
+#include "../../src/gpu/text_pack_codec.h"
 #include "../../src/gpu/text_pack_dense.h"
 #include "./testing.h"
 
@@ -299,7 +300,7 @@ TEST(TextPackDense, PoolRangesInAnyOrder) {
       job.ratio = -1.0;
       job.out = out.data() + ((64 - (reinterpret_cast<uintptr_t>(out.data()) & 63)) & 63);
       {
-        PackPool pool(threads, alphabet, 0, rb, PackCode::kDense);
+        PackPool pool(threads, MakePackCodec(PackCode::kDense, false, ','), 0, rb);
         pool.Push(&job);
         pool.Wait(&job);
       }
@@ -338,7 +339,7 @@ TEST(TextPackDense, PoolThreeQuarterRule) {
   job.ptr = text.data();
   job.size = text.size();
   job.out = out.data() + ((64 - (reinterpret_cast<uintptr_t>(out.data()) & 63)) & 63);
-  PackPool pool(2, alphabet, 0, 4, PackCode::kDense);
+  PackPool pool(2, MakePackCodec(PackCode::kDense, false, ','), 0, 4);
   pool.Push(&job);
   pool.Wait(&job);
   EXPECT_EQ(job.state.load(), static_cast<int>(PackJob::kRejected));
