@@ -3,7 +3,9 @@
 The reference (dmlc-core) ships no model; its consumers (XGBoost, linear
 learners in ps-lite/rabit) train on RowBlocks.  These demonstrators close the
 loop on MI355X: device CSR from the GPU parser -> HIP SpMV / SpMM -> loss ->
-gradient all-reduced over RCCL.
+gradient all-reduced over RCCL.  The tree side is
+:class:`SparseGBDT`: histogram gradient boosting on the column-major binned
+matrix of the same CSR.
 """
 from __future__ import annotations
 
@@ -11,11 +13,12 @@ from typing import Optional
 
 import torch
 
+from .. import ops
 from ..ops import (_stream, csr_ffm, csr_spmm, csr_spmv, hashed_dense, ndcg, qid_groups,
                    rank_loss)
 
 __all__ = ["SparseLogReg", "HashedFM", "SparseSoftmaxReg", "SparseFM", "SparseFFM",
-           "SparseRanker"]
+           "SparseRanker", "SparseGBDT"]
 
 
 class SparseLogReg(torch.nn.Module):
@@ -392,6 +395,151 @@ class _HashedFMFunction(torch.autograd.Function):
         _dmlc().fm_reduce_grads(part.data_ptr(), nblk, dim, vf.data_ptr(), ctx.sx, z.data_ptr(),
                                 gw.data_ptr(), gv.data_ptr(), _stream())
         return None, None, gw.to(v.dtype), gv.to(v.dtype), g.sum().reshape(1)
+
+
+class SparseGBDT:
+    """Histogram gradient-boosted trees on a device CSR (the XGBoost ``hist``
+    method on sparse rows): quantile cuts and 8-bit bins once
+    (:func:`~dmlc_core_amd.ops.feature_cuts`,
+    :func:`~dmlc_core_amd.ops.bin_features`), then per tree level
+    :func:`~dmlc_core_amd.ops.grad_histogram` ->
+    :func:`~dmlc_core_amd.ops.best_splits` ->
+    :func:`~dmlc_core_amd.ops.advance_rows`.  An absent entry is a missing
+    value and follows each split's learnt default side.  Device only: a host
+    CSR raises ``ValueError``.
+
+    Growth is depth-wise.  A tree is four tensors in heap layout (the children
+    of node i are 2i + 1 and 2i + 2) of ``2**(max_depth + 1) - 1`` nodes:
+    ``feature`` int64 (-1: a leaf), ``bin`` int32 (go left when the entry's bin
+    is ``<= bin``; the float threshold is ``cut[cut_ptr[feature] + bin]``),
+    ``default_left`` bool and ``leaf`` float32, ``-lr G / (H + lambda)`` of the
+    node's rows.  Level d is the node window ``first_node = 2**d - 1``,
+    ``num_nodes = 2**d``; rows of a node that did not split stay on its id,
+    outside every deeper window.  Objectives: ``"logistic"`` (labels in
+    [0, 1], margins are logits) and ``"squared"``; margins start at 0.
+    Gradients are summed as 64-bit fixed point, so a run is reproducible bit
+    for bit."""
+
+    def __init__(self, num_features: int, max_bins: int = 256, max_depth: int = 6,
+                 learning_rate: float = 0.3, reg_lambda: float = 1.0, gamma: float = 0.0,
+                 min_child_weight: float = 1.0, objective: str = "logistic"):
+        if objective not in ("logistic", "squared"):
+            raise ValueError(f"objective must be 'logistic' or 'squared', got {objective!r}")
+        if not 1 <= int(max_depth) <= 14:
+            raise ValueError(f"max_depth must be in [1, 14], got {max_depth!r}")
+        if not float(reg_lambda) > 0:
+            raise ValueError(f"reg_lambda must be > 0, got {reg_lambda!r}")
+        self.num_features, self.max_bins = int(num_features), int(max_bins)
+        self.max_depth, self.learning_rate = int(max_depth), float(learning_rate)
+        self.reg_lambda, self.gamma = float(reg_lambda), float(gamma)
+        self.min_child_weight, self.objective = float(min_child_weight), objective
+        self.cuts = None    # feature_cuts of the training data
+        self.trees = []     # dicts of feature / bin / default_left / leaf
+        self.margin = None  # the training rows' margins, updated by boost()
+
+    @staticmethod
+    def _device_csr(csr) -> None:
+        if not csr["index"].is_cuda:
+            raise ValueError("SparseGBDT runs on a device CSR (csr_to_torch of a GPU parse)")
+
+    def _gradients(self, margin, label, weight):
+        if self.objective == "logistic":
+            p = torch.sigmoid(margin)
+            g, h = p - label, p * (1.0 - p)
+        else:
+            g, h = margin - label, torch.ones_like(margin)
+        if weight is not None:
+            g, h = g * weight, h * weight
+        return g.contiguous(), h.contiguous()
+
+    def loss(self, margin: torch.Tensor, label: torch.Tensor, weight=None) -> torch.Tensor:
+        """the objective's mean loss of ``margin`` (``mean(weight * loss)``)"""
+        return _fm_loss(margin, label, weight, self.objective)
+
+    def fit(self, csr, rounds: int) -> "SparseGBDT":
+        """Cuts and bins of ``csr`` once, then ``rounds`` trees against
+        ``csr["label"]`` (row-weighted by ``csr["weight"]`` if present)."""
+        self._device_csr(csr)
+        self.cuts = ops.feature_cuts(csr, self.num_features, self.max_bins)
+        binned = ops.bin_features(csr, self.cuts, self.num_features)
+        self.trees, self.margin = [], None
+        label, weight = csr["label"].float(), csr.get("weight")
+        for _ in range(int(rounds)):
+            self.boost(binned, label, weight)
+        return self
+
+    def boost(self, binned, label: torch.Tensor, weight=None) -> torch.Tensor:
+        """Grow one tree on ``binned`` and return the updated training margins
+        (kept in ``self.margin``; they start at 0)."""
+        rows, dev = int(binned["rows"]), binned["row"].device
+        if self.cuts is None:
+            self.cuts = {"cut_ptr": binned["cut_ptr"], "cut": binned["cut"]}
+        if self.margin is None:
+            self.margin = torch.zeros(rows, dtype=torch.float32, device=dev)
+        elif self.margin.numel() != rows:
+            raise ValueError(f"SparseGBDT.boost: the model tracks the margins of "
+                             f"{self.margin.numel()} training rows, binned has {rows}: the trees "
+                             "were grown on another matrix (fit() starts a new model)")
+        label = label.to(device=dev, dtype=torch.float32)
+        g, h = self._gradients(self.margin, label, weight)
+        scale = ops.gradient_scale(g, h)
+        qgh = torch.stack([torch.round(g.double() * scale), torch.round(h.double() * scale)],
+                          1).long()
+        size = 2 ** (self.max_depth + 1) - 1
+        tree = {"feature": torch.full((size,), -1, dtype=torch.int64, device=dev),
+                "bin": torch.zeros(size, dtype=torch.int32, device=dev),
+                "default_left": torch.zeros(size, dtype=torch.bool, device=dev),
+                "leaf": torch.zeros(size, dtype=torch.float32, device=dev)}
+        pos = torch.zeros(rows, dtype=torch.int32, device=dev)
+        for depth in range(self.max_depth + 1):
+            first, n = 2 ** depth - 1, 2 ** depth
+            ids = torch.arange(first, first + n, dtype=torch.int32, device=dev)
+            node = pos.long() - first
+            live = (node >= 0) & (node < n)
+            node_sum = torch.zeros((n, 2), dtype=torch.int64, device=dev)
+            node_sum.index_add_(0, node[live], qgh[live])
+            sums = node_sum.double() / scale
+            tree["leaf"][first:first + n] = \
+                (-self.learning_rate * sums[:, 0] / (sums[:, 1] + self.reg_lambda)).float()
+            if depth == self.max_depth:
+                break
+            hist = ops.grad_histogram(binned, g, h, pos, n, scale, first_node=first)
+            split = ops.best_splits(hist, node_sum, binned["cut_ptr"], scale, self.reg_lambda,
+                                    self.gamma, self.min_child_weight)
+            for k in ("feature", "bin", "default_left"):
+                tree[k][first:first + n] = split[k]
+            pos = ops.advance_rows(binned, pos, split, *self._children(split, ids), first_node=first)
+        self.trees.append(tree)
+        self.margin = self.margin + tree["leaf"][pos.long()]
+        return self.margin
+
+    @staticmethod
+    def _children(split, ids):
+        """the ids a level's rows move to: 2i + 1 / 2i + 2, a leaf's rows stay on i"""
+        is_leaf = split["feature"] < 0
+        return (torch.where(is_leaf, ids, 2 * ids + 1).contiguous(),
+                torch.where(is_leaf, ids, 2 * ids + 2).contiguous())
+
+    def predict(self, csr) -> torch.Tensor:
+        """The margins of the rows of ``csr`` (logits under ``"logistic"``):
+        binned with the stored cuts, walked down every tree level by level."""
+        self._device_csr(csr)
+        if self.cuts is None:
+            raise ValueError("SparseGBDT.predict: the model has no cuts (fit or boost first)")
+        binned = ops.bin_features(csr, self.cuts, self.num_features)
+        rows, dev = int(binned["rows"]), binned["row"].device
+        margin = torch.zeros(rows, dtype=torch.float32, device=dev)
+        for tree in self.trees:
+            pos = torch.zeros(rows, dtype=torch.int32, device=dev)
+            for depth in range(self.max_depth):
+                first, n = 2 ** depth - 1, 2 ** depth
+                ids = torch.arange(first, first + n, dtype=torch.int32, device=dev)
+                split = {k: tree[k][first:first + n].contiguous()
+                         for k in ("feature", "bin", "default_left")}
+                pos = ops.advance_rows(binned, pos, split, *self._children(split, ids),
+                                       first_node=first)
+            margin = margin + tree["leaf"][pos.long()]
+        return margin
 
 
 _FM_LOSSES = {"logistic": 0, "squared": 1}

@@ -3,7 +3,10 @@
 Every op launches a hand-written CDNA4 kernel from ``libdmlc.so`` on the
 current torch stream (src/gpu/feature_kernels.hip, spmm_kernels.hip,
 transpose_kernels.hip, gather_kernels.hip, ffm_kernels.hip, rank_kernels.hip,
-compact_kernels.hip, optim_kernels.hip).
+compact_kernels.hip, optim_kernels.hip, gbdt_kernels.hip).
+Histogram gradient-boosted trees run on the column-major binned matrix:
+:func:`feature_cuts` -> :func:`bin_features` once, then per tree level
+:func:`grad_histogram` -> :func:`best_splits` -> :func:`advance_rows`.
 There is no PyTorch fallback: on a machine without the extension or a GPU these
 functions raise.
 
@@ -24,7 +27,9 @@ __all__ = ["spmv", "spmv_t", "hashed_dense", "SpMVFunction", "csr_spmv", "transp
            "compact_features", "lazy_update_",
            "spmm", "spmm_t", "SpMMFunction", "csr_spmm",
            "ffm", "ffm_t", "FFMFunction", "csr_ffm",
-           "qid_groups", "group_rows", "rank_loss", "rank_loss_parts", "RankLossFunction", "ndcg"]
+           "qid_groups", "group_rows", "rank_loss", "rank_loss_parts", "RankLossFunction", "ndcg",
+           "feature_cuts", "bin_features", "gradient_scale", "grad_histogram", "best_splits",
+           "advance_rows"]
 
 # persistent transpose scratch per (device, stream), grow-only: a rebuild (a
 # further shard, a refreshed batch) allocates no multi-GB scratch again
@@ -1196,3 +1201,290 @@ def csr_spmm(csr: Dict, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
     if grad not in ("auto", "transpose", "atomic"):
         raise ValueError(f"grad must be 'auto', 'transpose' or 'atomic', got {grad!r}")
     return SpMMFunction.apply(w, bias, (csr["offset"], csr["index"], csr.get("value")), csr, grad)
+
+
+# ------------------------------------------------------------ histogram GBDT
+def _gbdt_index64(csr: Dict, lo: int, hi: int) -> torch.Tensor:
+    """the feature ids of entries [lo, hi) as int64 (ids are < 2^28: checked by the transpose)"""
+    idx = csr["index"][lo:hi]
+    if idx.element_size() == 8:
+        return idx if idx.dtype == torch.int64 else idx.view(torch.int64)
+    idx = idx if idx.dtype == torch.int32 else idx.view(torch.int32)
+    return idx.long() & 0xFFFFFFFF
+
+
+def _check_cuts(name: str, cuts: Dict, num_features: int, dev) -> None:
+    cut_ptr, cut = cuts.get("cut_ptr"), cuts.get("cut")
+    if not isinstance(cut_ptr, torch.Tensor) or cut_ptr.dtype != torch.int64 \
+            or tuple(cut_ptr.shape) != (num_features + 1,):
+        raise ValueError(f"{name}: cut_ptr must be int64 [{num_features + 1}]")
+    if not isinstance(cut, torch.Tensor) or cut.dtype != torch.float32 or cut.dim() != 1:
+        raise ValueError(f"{name}: cut must be a 1-D float32 tensor")
+    for k, t in (("cut_ptr", cut_ptr), ("cut", cut)):
+        if t.device != dev or not t.is_contiguous():
+            raise ValueError(f"{name}: {k} must be a contiguous tensor on {dev}")
+
+
+def feature_cuts(csr: Dict, num_features: int, max_bins: int = 256) -> Dict:
+    """The quantile cuts of every feature of a device CSR (GB1,
+    src/gpu/gbdt_kernels.hip): ``{"cut_ptr": int64 [F + 1], "cut": float32
+    [total]}``, feature j's cuts ascending at ``cut[cut_ptr[j]:cut_ptr[j + 1]]``.
+
+    An absent entry is *missing*, not zero; a CSR without ``value`` reads every
+    entry as 1.0.  With s the n present values of a feature, ascending, and B =
+    ``max_bins`` (2 .. 256), the candidates are ``s[(i*n + B-1)//B - 1]`` for
+    i = 1 .. B; equal candidates collapse, so the last cut is the column's
+    maximum, n <= B makes every distinct value a cut, and n = 0 gives none.
+    Values compare as floats (-0.0 is +0.0), +-inf are ordinary values, a NaN
+    raises ``ValueError``.
+
+    torch does the plumbing: :func:`transpose` (cached in ``csr`` as the
+    gradients' is) gives the column counts and checks ``id < num_features <=
+    _dmlc.csr_transpose_max_features()``, one ``torch.sort`` orders an int64 key
+    per entry, ``(feature << 32) | order-preserving u32 of the value``.  GB1
+    then picks and de-duplicates every column's candidates, one wave per
+    column, in two runs around a ``cumsum`` of the counts.  Takes the CSR
+    shapes of :func:`transpose` (32- / 64-bit indices, a row slice).  Three
+    device-to-host reads: the slice's first entry ``offset[0]``, the total
+    number of cuts and the error word (a transpose that is not cached yet reads
+    the slice's ends once more)."""
+    if isinstance(max_bins, bool) or not isinstance(max_bins, int) \
+            or not 2 <= max_bins <= int(_dmlc.gbdt_max_bins()):
+        raise ValueError(f"feature_cuts: max_bins must be an int in [2, "
+                         f"{int(_dmlc.gbdt_max_bins())}], got {max_bins!r}")
+    csr_u = _unpair(csr)
+    t = _cached_transpose(csr, csr_u, int(num_features), "transpose")
+    num_features = int(num_features)
+    dev = csr_u["index"].device
+    nnz = int(t["index"].numel())
+    off = csr_u["offset"]
+    off = off.view(torch.int64) if off.dtype != torch.int64 else off
+    lo = int(off[0].item()) if off.numel() > 1 else 0
+    cut_ptr = torch.zeros(num_features + 1, dtype=torch.int64, device=dev)
+    if nnz == 0:
+        return {"cut_ptr": cut_ptr, "cut": torch.empty(0, dtype=torch.float32, device=dev)}
+    value = csr_u.get("value")
+    if value is None:
+        bits = torch.full((nnz,), 0x3F800000, dtype=torch.int64, device=dev)
+    else:
+        bits = (value[lo:lo + nnz] + 0.0).view(torch.int32).long()  # + 0.0: -0.0 becomes +0.0
+    ordered = torch.where(bits < 0, ~bits, bits + 0x80000000)
+    keys = torch.sort((_gbdt_index64(csr_u, lo, lo + nnz) << 32) | ordered).values
+    del bits, ordered
+    columns = {"offset": t["offset"], "index": t["index"], "value": t.get("value")}
+    view = _describe(columns, pairs=True)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    stream = _stream()
+    _dmlc.gbdt_cut_count(_ptr(keys), view, nnz, max_bins, _ptr(cut_ptr) + 8, _ptr(err), stream)
+    cut_ptr[1:].cumsum_(0)
+    total, bad = int(cut_ptr[-1].item()), int(err.item())
+    if bad:
+        raise ValueError("feature_cuts: a value is NaN")
+    cut = torch.empty(total, dtype=torch.float32, device=dev)
+    _dmlc.gbdt_cut_emit(_ptr(keys), view, nnz, max_bins, _ptr(cut_ptr), _ptr(cut), total, stream)
+    return {"cut_ptr": cut_ptr, "cut": cut}
+
+
+def bin_features(csr: Dict, cuts: Dict, num_features: int) -> Dict:
+    """The column-major binned matrix of a device CSR under ``cuts`` (GB2):
+    ``{"offset": int64 [F + 1], "row": int32 [nnz], "bin": uint8 [nnz],
+    "cut_ptr", "cut", "rows": int}`` -- the :func:`transpose` (cached in
+    ``csr``) with every value replaced by its bin; rows ascend within a column.
+
+    ``bin = min(#cuts of the column that are < x, ncuts - 1)``: a value equal
+    to a cut falls in that cut's bin, values below the first cut go to bin 0
+    and values above the last to the last bin (data that the cuts were not
+    trained on).  Entries of a feature without cuts get bin 0 and are ignored
+    by every later step.  The global bin of an entry of feature f is
+    ``cut_ptr[f] + bin``.  A NaN raises ``ValueError``, as does a feature with
+    more than 256 cuts.  One workgroup per ``_dmlc.gbdt_segment_entries()``
+    entries searches its columns' cuts in LDS.  Two device-to-host reads: the
+    check of ``cut_ptr`` and the error word."""
+    num_features = int(num_features)
+    csr_u = _unpair(csr)
+    dev = csr_u["index"].device
+    _check_cuts("bin_features", cuts, num_features, dev)
+    t = _cached_transpose(csr, csr_u, num_features, "transpose")
+    cut_ptr, cut = cuts["cut_ptr"], cuts["cut"]
+    widths = cut_ptr[1:] - cut_ptr[:-1]
+    ok = (widths.min() >= 0) & (widths.max() <= int(_dmlc.gbdt_max_bins())) \
+        & (cut_ptr[0] == 0) & (cut_ptr[-1] == cut.numel())
+    if not bool(ok.item()):
+        raise ValueError("bin_features: cut_ptr must ascend from 0 to len(cut) in steps of at most "
+                         f"{int(_dmlc.gbdt_max_bins())}")
+    nnz = int(t["index"].numel())
+    row = torch.empty(nnz, dtype=torch.int32, device=dev)
+    bins = torch.empty(nnz, dtype=torch.uint8, device=dev)
+    if nnz > 0:
+        columns = {"offset": t["offset"], "index": t["index"], "value": t.get("value")}
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+        _dmlc.gbdt_bin(_describe(columns, pairs=True), nnz, _ptr(cut_ptr), _ptr(cut), _ptr(row),
+                       _ptr(bins), _ptr(err), _stream())
+        if int(err.item()):
+            raise ValueError("bin_features: a value is NaN")
+    return {"offset": t["offset"], "row": row, "bin": bins, "cut_ptr": cut_ptr, "cut": cut,
+            "rows": int(csr_u["offset"].numel() - 1)}
+
+
+def _binned_arg(name: str, binned: Dict) -> tuple:
+    """``binned`` as the GB3 / GB5 bindings take it (gpu::GbdtBinned), checked"""
+    for k, dt in (("offset", torch.int64), ("row", torch.int32), ("bin", torch.uint8),
+                  ("cut_ptr", torch.int64)):
+        t = binned.get(k)
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1 or not t.is_cuda \
+                or not t.is_contiguous():
+            raise ValueError(f"{name}: binned[{k!r}] must be a contiguous 1-D {dt} device tensor")
+    offset, row, bins, cut_ptr = (binned[k] for k in ("offset", "row", "bin", "cut_ptr"))
+    if offset.numel() < 2 or cut_ptr.numel() != offset.numel() or bins.numel() != row.numel():
+        raise ValueError(f"{name}: binned's arrays do not fit each other")
+    return (_ptr(offset), _ptr(row), _ptr(bins), _ptr(cut_ptr), offset.numel() - 1, row.numel(),
+            int(binned["rows"]), int(binned["cut"].numel()))
+
+
+def _check_rows(name: str, what: str, t, dtype, rows: int, dev) -> None:
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != (rows,) \
+            or t.device != dev or not t.is_contiguous():
+        raise ValueError(f"{name}: {what} must be a contiguous {dtype} tensor [{rows}] on {dev}")
+
+
+def _check_window(name: str, num_nodes, first_node) -> None:
+    nmax = int(_dmlc.gbdt_max_nodes())
+    if isinstance(num_nodes, bool) or not isinstance(num_nodes, int) or not 1 <= num_nodes <= nmax:
+        raise ValueError(f"{name}: num_nodes must be an int in [1, {nmax}], got {num_nodes!r}")
+    if isinstance(first_node, bool) or not isinstance(first_node, int) \
+            or not 0 <= first_node < (1 << 30):
+        raise ValueError(f"{name}: first_node must be an int in [0, 2^30), got {first_node!r}")
+
+
+def gradient_scale(grad: torch.Tensor, hess: torch.Tensor) -> float:
+    """The power of two ``2**e`` that :func:`grad_histogram` quantises with:
+    ``e = 61 - ceil(log2(S))``, ``S = max(sum|g|, sum|h|)`` summed in float64
+    (1.0 for S = 0): every sum of quantised values stays below 2^62.  One
+    device-to-host read."""
+    import math
+    s = float(torch.stack([grad.double().abs().sum(), hess.double().abs().sum()]).max().item())
+    if not math.isfinite(s):
+        raise ValueError("gradient_scale: the gradients are not finite")
+    if s == 0.0:
+        return 1.0
+    m, k = math.frexp(s)  # s = m 2^k, m in [0.5, 1): ceil(log2 s) = k, or k - 1 at a power of two
+    return math.ldexp(1.0, 61 - (k - 1 if m == 0.5 else k))
+
+
+def grad_histogram(binned: Dict, grad: torch.Tensor, hess: torch.Tensor, pos: torch.Tensor,
+                   num_nodes: int, scale: float, first_node: int = 0) -> torch.Tensor:
+    """The gradient histograms of ``num_nodes`` tree nodes (GB3), int64
+    ``[num_nodes, total_bins, 2]``: a row r with ``n = pos[r] - first_node`` in
+    ``[0, num_nodes)`` adds ``(llrint(g[r] * scale), llrint(h[r] * scale))``
+    (float64 product, ties to even) at ``[n, cut_ptr[f] + bin, :]`` for each of
+    its entries; other rows are skipped.  Cells nothing fell in are 0.
+
+    ``grad`` / ``hess``: float32 ``[rows]``, ``pos``: int32 ``[rows]``,
+    ``scale``: :func:`gradient_scale`'s.  The sums are 64-bit integers, so they
+    do not depend on the order: two runs give the same bytes and a parent's
+    histogram is exactly the sum of its children's.  One workgroup per
+    ``_dmlc.gbdt_segment_entries()`` entries of the column-major matrix keeps
+    its (node, bin) sums in LDS, tiling the nodes when they do not fit, and
+    writes each cell once: by a plain store for a column inside one segment,
+    by one 64-bit atomic per non-zero cell for a column that spans several.
+    Nothing is read back."""
+    arg = _binned_arg("grad_histogram", binned)
+    _check_window("grad_histogram", num_nodes, first_node)
+    rows, total, dev = arg[6], arg[7], binned["row"].device
+    _check_rows("grad_histogram", "grad", grad, torch.float32, rows, dev)
+    _check_rows("grad_histogram", "hess", hess, torch.float32, rows, dev)
+    _check_rows("grad_histogram", "pos", pos, torch.int32, rows, dev)
+    if not float(scale) > 0:
+        raise ValueError(f"grad_histogram: scale must be > 0, got {scale!r}")
+    hist = torch.zeros((num_nodes, total, 2), dtype=torch.int64, device=dev)
+    if rows > 0 and total > 0 and arg[5] > 0:
+        _dmlc.gbdt_histogram(arg, _ptr(grad), _ptr(hess), _ptr(pos), first_node, num_nodes,
+                             float(scale), _ptr(hist), _stream())
+    return hist
+
+
+def best_splits(hist: torch.Tensor, node_sum: torch.Tensor, cut_ptr: torch.Tensor, scale: float,
+                reg_lambda: float = 1.0, gamma: float = 0.0,
+                min_child_weight: float = 1.0) -> Dict:
+    """The best split of every node (GB4): ``{"feature": int64 [N], "bin":
+    int32 [N], "default_left": bool [N], "gain": float64 [N]}``, ``feature``
+    -1 (bin 0, gain 0) for a node without a split.
+
+    ``hist``: :func:`grad_histogram`'s ``[N, total_bins, 2]``; ``node_sum``:
+    int64 ``[N, 2]``, the quantised totals of each node's rows, rows without an
+    entry in a feature included.  For a feature with c >= 1 cuts every
+    threshold t in 0 .. c-1 and both sides for the missing rows is a candidate:
+    left = bins <= t (plus ``node_sum - column total`` when missing goes left),
+    right = the rest; the integer sums become float64 and are divided by
+    ``scale``; valid with ``HL, HR >= min_child_weight``;
+    ``gain = 0.5*(GL^2/(HL+l) + GR^2/(HR+l) - G^2/(H+l)) - gamma``.  The answer
+    is the valid candidate of greatest gain if that is > 0; equal gains go to
+    the lowest (feature, bin), then to missing-right -- a total order, so
+    every run gives the same answer.  The float threshold of a split is
+    ``cut[cut_ptr[feature] + bin]``.  ``reg_lambda`` must be > 0."""
+    if not isinstance(hist, torch.Tensor) or hist.dtype != torch.int64 or hist.dim() != 3 \
+            or hist.shape[2] != 2 or not hist.is_cuda or not hist.is_contiguous():
+        raise ValueError("best_splits: hist must be a contiguous int64 device tensor [N, bins, 2]")
+    n, total, dev = int(hist.shape[0]), int(hist.shape[1]), hist.device
+    if not isinstance(node_sum, torch.Tensor) or node_sum.dtype != torch.int64 \
+            or tuple(node_sum.shape) != (n, 2) or node_sum.device != dev \
+            or not node_sum.is_contiguous():
+        raise ValueError(f"best_splits: node_sum must be a contiguous int64 tensor [{n}, 2] on {dev}")
+    if not isinstance(cut_ptr, torch.Tensor) or cut_ptr.dtype != torch.int64 or cut_ptr.dim() != 1 \
+            or cut_ptr.numel() < 2 or cut_ptr.device != dev or not cut_ptr.is_contiguous():
+        raise ValueError(f"best_splits: cut_ptr must be a contiguous int64 tensor [F + 1] on {dev}")
+    if not float(reg_lambda) > 0:
+        raise ValueError(f"best_splits: reg_lambda must be > 0, got {reg_lambda!r}")
+    if not float(scale) > 0:
+        raise ValueError(f"best_splits: scale must be > 0, got {scale!r}")
+    if n > int(_dmlc.gbdt_max_nodes()):
+        raise ValueError(f"best_splits: at most {int(_dmlc.gbdt_max_nodes())} nodes, got {n}")
+    nfeat = cut_ptr.numel() - 1
+    res = {"feature": torch.full((n,), -1, dtype=torch.int64, device=dev),
+           "bin": torch.zeros(n, dtype=torch.int32, device=dev),
+           "default_left": torch.zeros(n, dtype=torch.bool, device=dev),
+           "gain": torch.zeros(n, dtype=torch.float64, device=dev)}
+    if n > 0:
+        ws = _workspace(int(_dmlc.gbdt_split_scratch_bytes(n, nfeat)) + 16, dev)
+        _dmlc.gbdt_best_splits(_ptr(hist), _ptr(node_sum), _ptr(cut_ptr), nfeat, total, n,
+                               float(scale), float(reg_lambda), float(gamma),
+                               float(min_child_weight), (_ptr(ws) + 15) // 16 * 16,
+                               _ptr(res["feature"]), _ptr(res["bin"]), _ptr(res["default_left"]),
+                               _ptr(res["gain"]), _stream())
+    return res
+
+
+def advance_rows(binned: Dict, pos: torch.Tensor, split: Dict, left: torch.Tensor,
+                 right: torch.Tensor, first_node: int = 0) -> torch.Tensor:
+    """Every row's node after the splits of one tree level (GB5), a new int32
+    ``[rows]``: a row in node n of the window (``pos[r] == first_node + n``, n <
+    N) goes to ``left[n]`` if ``split["feature"][n] < 0``; else, with an entry
+    in that column, to ``left[n]`` when its bin is ``<= split["bin"][n]`` and
+    to ``right[n]`` otherwise; and without an entry to the side
+    ``split["default_left"][n]`` names.  Rows outside the window keep their
+    ``pos``.  ``left`` / ``right``: int32 ``[N]``, the ids the children get.
+
+    One pass over ``pos``, then only the split columns are read, filtered by
+    ``pos == n`` (two nodes may split on the same feature).  A row's feature
+    ids are taken to be distinct; with a repeated id the result is
+    unspecified.  Nothing is read back."""
+    arg = _binned_arg("advance_rows", binned)
+    rows, dev = arg[6], binned["row"].device
+    _check_rows("advance_rows", "pos", pos, torch.int32, rows, dev)
+    feature = split.get("feature")
+    if not isinstance(feature, torch.Tensor) or feature.dim() != 1:
+        raise ValueError("advance_rows: split['feature'] must be a 1-D tensor")
+    n = int(feature.numel())
+    _check_window("advance_rows", max(n, 1), first_node)
+    _check_rows("advance_rows", "split['feature']", feature, torch.int64, n, dev)
+    _check_rows("advance_rows", "split['bin']", split.get("bin"), torch.int32, n, dev)
+    _check_rows("advance_rows", "split['default_left']", split.get("default_left"), torch.bool, n,
+                dev)
+    _check_rows("advance_rows", "left", left, torch.int32, n, dev)
+    _check_rows("advance_rows", "right", right, torch.int32, n, dev)
+    out = torch.empty_like(pos)
+    if rows > 0:
+        _dmlc.gbdt_advance(arg, _ptr(pos), _ptr(feature), _ptr(split["bin"]),
+                           _ptr(split["default_left"]), _ptr(left), _ptr(right), first_node, n,
+                           _ptr(out), _stream())
+    return out

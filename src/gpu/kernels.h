@@ -34,6 +34,11 @@
  *   U3 compact emit      LaunchCompactEmit        (compact_kernels.hip)
  *   U4 compact remap     LaunchCompactRemap       (compact_kernels.hip)
  *   L1 lazy row update   LaunchLazyUpdate         (optim_kernels.hip)
+ *   GB1 quantile cuts    LaunchGbdtCutCount, LaunchGbdtCutEmit (gbdt_kernels.hip)
+ *   GB2 bin features     LaunchGbdtBin            (gbdt_kernels.hip)
+ *   GB3 grad histogram   LaunchGbdtHistogram      (gbdt_kernels.hip)
+ *   GB4 best splits      LaunchGbdtBestSplits     (gbdt_kernels.hip)
+ *   GB5 advance rows     LaunchGbdtAdvance        (gbdt_kernels.hip)
  * The launchers of K9, K11, M1 / M2, FF1 / FF2, G2 and the transpose take
  * their CSR operand as one CsrView and pick the kernel for its index width
  * (and pair layout) themselves; launch_common.h holds what they share.
@@ -717,6 +722,86 @@ constexpr uint32_t kLazyErrIds = 1;
 void LaunchLazyUpdate(int rule, float* param, const int64_t* ids, const float* grad, float* state0,
                       float* state1, uint64_t features, uint64_t nrows, uint64_t width,
                       const LazyHyper& hyper, uint32_t* error, hipStream_t stream);
+// ------------------- histogram GBDT (gbdt_kernels.hip) -------------------
+/*! \brief entries of a column segment, the work unit of GB2 / GB3 (one workgroup) */
+constexpr uint32_t kGbdtSegmentEntries = 4096;
+uint64_t GbdtSegmentEntries();
+/*! \brief most cuts (bins) of a feature */
+constexpr uint32_t kGbdtMaxBins = 256;
+/*! \brief most nodes of one GB3 / GB4 / GB5 call (a tree level: depth 15) */
+constexpr uint32_t kGbdtMaxNodes = 1u << 15;
+/*! \brief bit GB1 / GB2 OR into their error word: a value is NaN */
+constexpr uint32_t kGbdtErrNaN = 1;
+/*!
+ * \brief the column-major binned matrix: offset [num_features + 1] (from 0),
+ *  row / bin [nnz] (rows ascending within a column, bin < the column's cuts),
+ *  cut_ptr [num_features + 1] ending at total_bins; `rows` bounds every row id
+ */
+struct GbdtBinned {
+  const int64_t* offset;
+  const int32_t* row;
+  const uint8_t* bin;
+  const int64_t* cut_ptr;
+  uint64_t num_features, nnz, rows, total_bins;
+};
+/*!
+ * \brief GB1, first run: counts[f] = distinct quantile candidates of column f,
+ *  for keys [nnz] = (feature << 32 | order-preserving u32 of the value) sorted
+ *  ascending and the column pointer of `columns` (a transpose of the same
+ *  entries: offset [nrows + 1] from 0).  The candidates of a column of n
+ *  values s are s[(i n + B - 1) / B - 1], i = 1 .. B = max_bins (2 .. 256).
+ *  A column whose first or last value is a NaN ORs kGbdtErrNaN into *error.
+ */
+void LaunchGbdtCutCount(const int64_t* keys, const CsrView& columns, uint64_t nnz, uint32_t max_bins,
+                        int64_t* counts, uint32_t* error, hipStream_t stream);
+/*! \brief GB1, second run: the candidates kept, ascending, as cut[cut_ptr[f] ..);
+ *  cut_ptr: the exclusive scan of the counts; a position at or past capacity is not written */
+void LaunchGbdtCutEmit(const int64_t* keys, const CsrView& columns, uint64_t nnz, uint32_t max_bins,
+                       const int64_t* cut_ptr, float* cut, uint64_t capacity, hipStream_t stream);
+/*!
+ * \brief GB2: for the nnz entries of `columns` (a transpose, pairs or separate
+ *  arrays, value may be null: 1.0) row_out[j] = row id and bin_out[j] =
+ *  min(#cuts of its column < x, ncuts - 1), 0 for a column without cuts.  No
+ *  column may have more than kGbdtMaxBins cuts.  A NaN ORs kGbdtErrNaN.
+ */
+void LaunchGbdtBin(const CsrView& columns, uint64_t nnz, const int64_t* cut_ptr, const float* cut,
+                   int32_t* row_out, uint8_t* bin_out, uint32_t* error, hipStream_t stream);
+/*!
+ * \brief GB3: hist[node, cut_ptr[f] + bin, :] += (llrint(g[r] scale), llrint(h[r]
+ *  scale)) over the entries (r, bin) of every column f, node = pos[r] -
+ *  first_node in [0, num_nodes) (other rows are skipped); hist: int64
+ *  [num_nodes x total_bins x 2], zeroed by the caller.  Sums are formed in LDS
+ *  per segment; integer sums: the same bytes on every run.
+ */
+void LaunchGbdtHistogram(const GbdtBinned& m, const float* grad, const float* hess,
+                         const int32_t* pos, int32_t first_node, uint32_t num_nodes, double scale,
+                         int64_t* hist, hipStream_t stream);
+/*! \brief bytes of 16-byte aligned scratch of LaunchGbdtBestSplits */
+size_t GbdtSplitScratchBytes(uint64_t num_nodes, uint64_t num_features);
+/*!
+ * \brief GB4: the best split of every node from hist (GB3) and node_sum [N x 2]
+ *  (the quantised totals of the node's rows): over features with cuts, bins t
+ *  and both sides for the rows without an entry, gain = 1/2 (GL^2 / (HL + l) +
+ *  GR^2 / (HR + l) - G^2 / (H + l)) - gamma in f64 on sums / scale, valid with
+ *  HL, HR >= min_child_weight, kept if > 0.  Equal gains: the lowest (feature,
+ *  bin), then missing-right.  feature[n] = -1 (bin 0, gain 0) without a split.
+ */
+void LaunchGbdtBestSplits(const int64_t* hist, const int64_t* node_sum, const int64_t* cut_ptr,
+                          uint64_t num_features, uint64_t total_bins, uint32_t num_nodes, double scale,
+                          double reg_lambda, double gamma, double min_child_weight, void* scratch,
+                          int64_t* feature, int32_t* bin, uint8_t* default_left, double* gain,
+                          hipStream_t stream);
+/*!
+ * \brief GB5: pos_out[r] for every row: a row of node n = pos_in[r] -
+ *  first_node in [0, num_nodes) goes to left[n] if feature[n] < 0, else by its
+ *  entry in column feature[n] (bin <= split_bin[n]: left[n], else right[n]),
+ *  and without one to the default side; other rows keep pos_in[r].  Reads pos
+ *  once and only the split columns.  pos_out != pos_in.
+ */
+void LaunchGbdtAdvance(const GbdtBinned& m, const int32_t* pos_in, const int64_t* feature,
+                       const int32_t* split_bin, const uint8_t* default_left, const int32_t* left,
+                       const int32_t* right, int32_t first_node, uint32_t num_nodes, int32_t* pos_out,
+                       hipStream_t stream);
 /*! \brief fill n floats with v */
 void LaunchFill(float* p, size_t n, float v, hipStream_t stream);
 /*!

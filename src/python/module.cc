@@ -1203,6 +1203,92 @@ PYBIND11_MODULE(_dmlc, m) {
   m.def("compact_scratch_bytes", &gpu::CompactScratchBytes, py::arg("num_features"),
         "bytes of 16-byte aligned scratch compact_mark / compact_emit share");
   m.attr("compact_err_index") = gpu::kCompactErrIndex;
+  // histogram GBDT (GB1 - GB5).  The binned matrix travels as
+  // (offset, row, bin, cut_ptr, num_features, nnz, rows, total_bins).
+  using BinnedArg = std::tuple<uintptr_t, uintptr_t, uintptr_t, uintptr_t, uint64_t, uint64_t,
+                               uint64_t, uint64_t>;
+  auto binned_of = [](const BinnedArg& a) {
+    return gpu::GbdtBinned{Ptr<const int64_t>(std::get<0>(a)), Ptr<const int32_t>(std::get<1>(a)),
+                           Ptr<const uint8_t>(std::get<2>(a)), Ptr<const int64_t>(std::get<3>(a)),
+                           std::get<4>(a), std::get<5>(a), std::get<6>(a), std::get<7>(a)};
+  };
+  m.def("gbdt_segment_entries", &gpu::GbdtSegmentEntries);
+  m.def("gbdt_max_bins", []() { return gpu::kGbdtMaxBins; });
+  m.def("gbdt_max_nodes", []() { return gpu::kGbdtMaxNodes; });
+  m.attr("gbdt_err_nan") = gpu::kGbdtErrNaN;
+  m.def(
+      "gbdt_cut_count",
+      [stream_of](uintptr_t keys, const CsrArg& columns, uint64_t nnz, uint32_t max_bins,
+                  uintptr_t counts, uintptr_t error, uintptr_t stream) {
+        gpu::LaunchGbdtCutCount(Ptr<const int64_t>(keys), View(columns), nnz, max_bins,
+                                Ptr<int64_t>(counts), Ptr<uint32_t>(error), stream_of(stream));
+      },
+      py::arg("keys"), py::arg("columns"), py::arg("nnz"), py::arg("max_bins"), py::arg("counts"),
+      py::arg("error"), py::arg("stream"));
+  m.def(
+      "gbdt_cut_emit",
+      [stream_of](uintptr_t keys, const CsrArg& columns, uint64_t nnz, uint32_t max_bins,
+                  uintptr_t cut_ptr, uintptr_t cut, uint64_t capacity, uintptr_t stream) {
+        gpu::LaunchGbdtCutEmit(Ptr<const int64_t>(keys), View(columns), nnz, max_bins,
+                               Ptr<const int64_t>(cut_ptr), Ptr<float>(cut), capacity,
+                               stream_of(stream));
+      },
+      py::arg("keys"), py::arg("columns"), py::arg("nnz"), py::arg("max_bins"), py::arg("cut_ptr"),
+      py::arg("cut"), py::arg("capacity"), py::arg("stream"));
+  m.def(
+      "gbdt_bin",
+      [stream_of](const CsrArg& columns, uint64_t nnz, uintptr_t cut_ptr, uintptr_t cut,
+                  uintptr_t row_out, uintptr_t bin_out, uintptr_t error, uintptr_t stream) {
+        gpu::LaunchGbdtBin(View(columns), nnz, Ptr<const int64_t>(cut_ptr), Ptr<const float>(cut),
+                           Ptr<int32_t>(row_out), Ptr<uint8_t>(bin_out), Ptr<uint32_t>(error),
+                           stream_of(stream));
+      },
+      py::arg("columns"), py::arg("nnz"), py::arg("cut_ptr"), py::arg("cut"), py::arg("row_out"),
+      py::arg("bin_out"), py::arg("error"), py::arg("stream"));
+  m.def(
+      "gbdt_histogram",
+      [stream_of, binned_of](const BinnedArg& binned, uintptr_t grad, uintptr_t hess, uintptr_t pos,
+                             int32_t first_node, uint32_t num_nodes, double scale, uintptr_t hist,
+                             uintptr_t stream) {
+        gpu::LaunchGbdtHistogram(binned_of(binned), Ptr<const float>(grad), Ptr<const float>(hess),
+                                 Ptr<const int32_t>(pos), first_node, num_nodes, scale,
+                                 Ptr<int64_t>(hist), stream_of(stream));
+      },
+      py::arg("binned"), py::arg("grad"), py::arg("hess"), py::arg("pos"), py::arg("first_node"),
+      py::arg("num_nodes"), py::arg("scale"), py::arg("hist"), py::arg("stream"));
+  m.def("gbdt_split_scratch_bytes", &gpu::GbdtSplitScratchBytes, py::arg("num_nodes"),
+        py::arg("num_features"));
+  m.def(
+      "gbdt_best_splits",
+      [stream_of](uintptr_t hist, uintptr_t node_sum, uintptr_t cut_ptr, uint64_t num_features,
+                  uint64_t total_bins, uint32_t num_nodes, double scale, double reg_lambda,
+                  double gamma, double min_child_weight, uintptr_t scratch, uintptr_t feature,
+                  uintptr_t bin, uintptr_t default_left, uintptr_t gain, uintptr_t stream) {
+        gpu::LaunchGbdtBestSplits(Ptr<const int64_t>(hist), Ptr<const int64_t>(node_sum),
+                                  Ptr<const int64_t>(cut_ptr), num_features, total_bins, num_nodes,
+                                  scale, reg_lambda, gamma, min_child_weight, Ptr<void>(scratch),
+                                  Ptr<int64_t>(feature), Ptr<int32_t>(bin),
+                                  Ptr<uint8_t>(default_left), Ptr<double>(gain), stream_of(stream));
+      },
+      py::arg("hist"), py::arg("node_sum"), py::arg("cut_ptr"), py::arg("num_features"),
+      py::arg("total_bins"), py::arg("num_nodes"), py::arg("scale"), py::arg("reg_lambda"),
+      py::arg("gamma"), py::arg("min_child_weight"), py::arg("scratch"), py::arg("feature"),
+      py::arg("bin"), py::arg("default_left"), py::arg("gain"), py::arg("stream"));
+  m.def(
+      "gbdt_advance",
+      [stream_of, binned_of](const BinnedArg& binned, uintptr_t pos_in, uintptr_t feature,
+                             uintptr_t split_bin, uintptr_t default_left, uintptr_t left,
+                             uintptr_t right, int32_t first_node, uint32_t num_nodes,
+                             uintptr_t pos_out, uintptr_t stream) {
+        gpu::LaunchGbdtAdvance(binned_of(binned), Ptr<const int32_t>(pos_in),
+                               Ptr<const int64_t>(feature), Ptr<const int32_t>(split_bin),
+                               Ptr<const uint8_t>(default_left), Ptr<const int32_t>(left),
+                               Ptr<const int32_t>(right), first_node, num_nodes,
+                               Ptr<int32_t>(pos_out), stream_of(stream));
+      },
+      py::arg("binned"), py::arg("pos_in"), py::arg("feature"), py::arg("split_bin"),
+      py::arg("default_left"), py::arg("left"), py::arg("right"), py::arg("first_node"),
+      py::arg("num_nodes"), py::arg("pos_out"), py::arg("stream"));
   m.def(
       "lazy_update",
       [stream_of](int rule, uintptr_t param, uintptr_t ids, uintptr_t grad, uintptr_t state0,
