@@ -21,8 +21,10 @@
  *  array of every page is one DMA straight into its place in a DeviceCSR --
  *  no parse, no host copy -- and one kernel rebases the page-local row
  *  pointers.  A binary page is ~half the bytes of its text, so a cached epoch
- *  moves ~2x the rows per second over the same PCIe link.  Remote or
- *  unregistrable files are read through dmlc::Stream into pinned staging.
+ *  moves ~2x the rows per second over the same PCIe link.  Where the runtime
+ *  cannot register a mapping the file is read into pinned memory once, at
+ *  Open, and every Load DMAs from there.  Remote or unmappable files are read
+ *  through dmlc::Stream into pinned staging.
  */
 #ifndef DMLC_GPU_DEVICE_PAGE_CACHE_H_
 #define DMLC_GPU_DEVICE_PAGE_CACHE_H_
@@ -75,7 +77,8 @@ class DevicePageCache {
   size_t nnz() const { return nnz_; }
   /*! \brief bytes of the cache file */
   size_t bytes() const { return bytes_; }
-  /*! \brief true when loads DMA straight from the registered file mapping */
+  /*! \brief true when loads DMA straight from the whole file held in
+   *  page-locked memory (registered mapping, or pinned copy), with no staging */
   bool zero_copy() const { return map_ != nullptr; }
   const std::vector<CachePage>& pages() const { return pages_; }
   uint64_t max_index() const { return max_index_; }
@@ -93,10 +96,12 @@ class DevicePageCache {
   size_t rows_{0}, nnz_{0}, bytes_{0};
   uint64_t max_index_{0}, max_field_{0};
   bool has_weight_{false}, has_qid_{false}, has_field_{false}, has_value_{false};
-  // zero-copy mapping (local files)
+  // the local file in page-locked memory: its registered mapping, or its
+  // bytes in a pinned allocation where registration does not work
   int fd_{-1};
   void* map_{nullptr};
   size_t map_len_{0};
+  bool map_registered_{false};
   std::unique_ptr<Stream> stream_;
   DeviceBuffer page_table_;
   PinnedBuffer page_table_host_;

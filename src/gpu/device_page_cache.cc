@@ -19,6 +19,7 @@
 
 #include "../io/filesys.h"
 #include "./kernels.h"
+#include "./pinned_file.h"
 
 namespace dmlc {
 namespace gpu {
@@ -42,10 +43,11 @@ bool IsLocal(const std::string& path) {
 template <typename IndexType>
 DevicePageCache<IndexType>::~DevicePageCache() {
   if (stream_ != nullptr) (void)hipStreamSynchronize(stream_->get());
-  if (map_ != nullptr) {
-    (void)hipHostUnregister(map_);
-    munmap(map_, map_len_);
-  }
+  PinnedFileRange pin;
+  pin.map = map_;
+  pin.map_len = map_len_;
+  pin.registered = map_registered_;
+  UnpinFileRange(&pin);
   if (fd_ >= 0) ::close(fd_);
 }
 
@@ -64,16 +66,12 @@ std::unique_ptr<DevicePageCache<IndexType>> DevicePageCache<IndexType>::Open(
     CHECK_EQ(fstat(c->fd_, &st), 0) << "cannot stat cache file " << path;
     c->bytes_ = static_cast<size_t>(st.st_size);
     if (c->bytes_ != 0) {
-      void* m = mmap(nullptr, c->bytes_, PROT_READ, MAP_SHARED | MAP_POPULATE, c->fd_, 0);
-      if (m != MAP_FAILED) {
-        DMLC_HIP_CHECK(hipSetDevice(device));
-        if (hipHostRegister(m, c->bytes_, hipHostRegisterReadOnly) == hipSuccess) {
-          c->map_ = m;
-          c->map_len_ = c->bytes_;
-        } else {
-          (void)hipGetLastError();
-          munmap(m, c->bytes_);
-        }
+      DMLC_HIP_CHECK(hipSetDevice(device));
+      PinnedFileRange pin;  // registered, or read into pinned memory once
+      if (PinFileRange(c->fd_, 0, c->bytes_, /*try_register=*/true, &pin)) {
+        c->map_ = pin.map;
+        c->map_len_ = pin.map_len;
+        c->map_registered_ = pin.registered;
       }
     }
   } else {

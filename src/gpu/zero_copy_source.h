@@ -21,6 +21,11 @@
  * `pin_budget` is per process; ShardPinBudget() divides the configured budget
  * among the ranks of a host and bounds it by the host's available memory.
  *
+ * Where hipHostRegister does not work on a file mapping (Init's probe finds
+ * out), a window is a hipHostMalloc allocation that the file range is read
+ * into (pinned_file.h): one host copy per window instead of none, in the same
+ * windows, with the same budget and the same pieces.
+ *
  * Chunks never cross a file boundary and end on a record boundary (a record
  * longer than chunk_bytes makes its chunk longer):
  *  - text: after the last EOL of the window (reference LineSplitter,
@@ -52,6 +57,7 @@
 
 #include "../io/filesys.h"
 #include "../io/input_split_base.h"
+#include "./pinned_file.h"
 
 namespace dmlc {
 namespace gpu {
@@ -99,10 +105,12 @@ class ZeroCopySource {
       segs_.push_back(Seg{fds_.size() - 1, seg.begin, seg.end - seg.begin, i});
     }
     windowed_ = PartitionBytes() > pin_budget;
-    // probe once: a file that cannot be mapped + registered fails here
+    // probe once: a file that cannot be page-locked either way fails here, and
+    // where registration does not work every window of this source is staged
     if (!segs_.empty()) {
       Mapping probe;
       if (!MapRange(segs_[0], 0, std::min(segs_[0].size, page_), &probe)) return Fail();
+      staged_ = !probe.registered;
       Unmap(&probe);
     }
     all_ = segs_;
@@ -246,31 +254,17 @@ class ZeroCopySource {
     size_t size;
     size_t init_index;  // position in the Init segment list (window key)
   };
-  struct Mapping {
-    void* map{nullptr};
-    size_t map_len{0};
+  struct Mapping : PinnedFileRange {
     const char* data{nullptr};  // segment byte seg_off
     size_t seg_index{0}, seg_off{0}, len{0};
-    bool registered{false};
   };
 
   bool MapRange(const Seg& s, size_t seg_off, size_t len, Mapping* m) {
     const size_t file_off = s.file_begin + seg_off;
     const size_t map_off = file_off & ~(page_ - 1);
-    m->map_len = file_off + len - map_off;
-    m->map = mmap(nullptr, m->map_len, PROT_READ, MAP_SHARED | MAP_POPULATE, fds_[s.fd_index],
-                  static_cast<off_t>(map_off));
-    if (m->map == MAP_FAILED) {
-      m->map = nullptr;
+    if (!PinFileRange(fds_[s.fd_index], map_off, file_off + len - map_off, !staged_, m)) {
       return false;
     }
-    if (hipHostRegister(m->map, m->map_len, hipHostRegisterReadOnly) != hipSuccess) {
-      (void)hipGetLastError();
-      munmap(m->map, m->map_len);
-      m->map = nullptr;
-      return false;
-    }
-    m->registered = true;
     {
       std::lock_guard<std::mutex> lk(pinned_mu_);
       pinned_ += m->map_len;
@@ -283,13 +277,11 @@ class ZeroCopySource {
   }
   void Unmap(Mapping* m) {
     if (m->map == nullptr) return;
-    if (m->registered) {
-      (void)hipHostUnregister(m->map);
+    {
       std::lock_guard<std::mutex> lk(pinned_mu_);
       pinned_ -= m->map_len;
     }
-    munmap(m->map, m->map_len);
-    m->map = nullptr;
+    UnpinFileRange(m);
   }
   /*! \brief finish the background registration; retained mode keeps its window */
   void JoinPending() {
@@ -432,6 +424,7 @@ class ZeroCopySource {
   Cut cut_;
   size_t chunk_bytes_{0}, page_{4096}, window_bytes_{1UL << 30};
   bool windowed_{false};
+  bool staged_{false};  // set by Init's probe, read-only afterwards
   std::vector<int> fds_;
   std::vector<Seg> segs_;
   std::vector<Seg> all_;  // the Init list (Reorder's source)
