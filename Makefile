@@ -55,6 +55,11 @@ $(BUILD)/obj/%.hip.o: src/%.hip $(HEADERS)
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+# GB6's margins are a chain of single f32 adds that must equal the level-by-level path bit for
+# bit: the compiler may not select packed f32 ops (v_pk_add/mul/fma_f32) in that file.  A
+# guard, not a tuning knob: see the header of forest_kernels.hip and profiles/gbdt/README.md
+$(BUILD)/obj/gpu/forest_kernels.hip.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+
 $(LIB): $(CPU_OBJS) $(HIP_OBJS)
 	@mkdir -p $(LIBDIR)
 	$(CXX) -o $@ $^ $(LDFLAGS_LIB)

@@ -436,6 +436,7 @@ class SparseGBDT:
         self.cuts = None    # feature_cuts of the training data
         self.trees = []     # dicts of feature / bin / default_left / leaf
         self.margin = None  # the training rows' margins, updated by boost()
+        self._packed = None  # ops.pack_forest of the trees, for predict(method="rows") / leaves()
 
     @staticmethod
     def _device_csr(csr) -> None:
@@ -462,7 +463,7 @@ class SparseGBDT:
         self._device_csr(csr)
         self.cuts = ops.feature_cuts(csr, self.num_features, self.max_bins)
         binned = ops.bin_features(csr, self.cuts, self.num_features)
-        self.trees, self.margin = [], None
+        self.trees, self.margin, self._packed = [], None, None
         label, weight = csr["label"].float(), csr.get("weight")
         for _ in range(int(rounds)):
             self.boost(binned, label, weight)
@@ -510,6 +511,7 @@ class SparseGBDT:
                 tree[k][first:first + n] = split[k]
             pos = ops.advance_rows(binned, pos, split, *self._children(split, ids), first_node=first)
         self.trees.append(tree)
+        self._packed = None
         self.margin = self.margin + tree["leaf"][pos.long()]
         return self.margin
 
@@ -520,26 +522,57 @@ class SparseGBDT:
         return (torch.where(is_leaf, ids, 2 * ids + 1).contiguous(),
                 torch.where(is_leaf, ids, 2 * ids + 2).contiguous())
 
-    def predict(self, csr) -> torch.Tensor:
-        """The margins of the rows of ``csr`` (logits under ``"logistic"``):
-        binned with the stored cuts, walked down every tree level by level."""
+    def _forest(self):
+        """the trees packed for GB6, repacked when their number has changed (and only then: a
+        tree replaced in place, or new ``cuts``, needs ``self._packed = None``)"""
+        if self._packed is None or self._packed["trees"] != len(self.trees):
+            self._packed = ops.pack_forest(self.trees, self.cuts)
+        return self._packed
+
+    def predict(self, csr, method: str = "levels") -> torch.Tensor:
+        """The margins of the rows of ``csr`` (logits under ``"logistic"``).
+        ``method="levels"``: binned with the stored cuts (a transpose of
+        ``csr``), walked down every tree level by level, one
+        :func:`~dmlc_core_amd.ops.advance_rows` per tree and level.
+        ``method="rows"``: one :func:`~dmlc_core_amd.ops.predict_forest` launch
+        over the rows as they lie (a minibatch off the parser or
+        :func:`~dmlc_core_amd.ops.gather_rows`), the packed forest cached on
+        the model; the same bytes."""
+        if method not in ("levels", "rows"):
+            raise ValueError(f"SparseGBDT.predict: method must be 'levels' or 'rows', got {method!r}")
         self._device_csr(csr)
         if self.cuts is None:
             raise ValueError("SparseGBDT.predict: the model has no cuts (fit or boost first)")
+        if method == "rows":
+            return ops.predict_forest(csr, self._forest(), "margin")
         binned = ops.bin_features(csr, self.cuts, self.num_features)
         rows, dev = int(binned["rows"]), binned["row"].device
         margin = torch.zeros(rows, dtype=torch.float32, device=dev)
         for tree in self.trees:
-            pos = torch.zeros(rows, dtype=torch.int32, device=dev)
-            for depth in range(self.max_depth):
-                first, n = 2 ** depth - 1, 2 ** depth
-                ids = torch.arange(first, first + n, dtype=torch.int32, device=dev)
-                split = {k: tree[k][first:first + n].contiguous()
-                         for k in ("feature", "bin", "default_left")}
-                pos = ops.advance_rows(binned, pos, split, *self._children(split, ids),
-                                       first_node=first)
-            margin = margin + tree["leaf"][pos.long()]
+            margin = margin + tree["leaf"][self._walk_levels(binned, tree).long()]
         return margin
+
+    def _walk_levels(self, binned, tree) -> torch.Tensor:
+        """the node every row of ``binned`` ends on in ``tree``, level by level (GB5)"""
+        dev = binned["row"].device
+        pos = torch.zeros(int(binned["rows"]), dtype=torch.int32, device=dev)
+        for depth in range(self.max_depth):
+            first, n = 2 ** depth - 1, 2 ** depth
+            ids = torch.arange(first, first + n, dtype=torch.int32, device=dev)
+            split = {k: tree[k][first:first + n].contiguous()
+                     for k in ("feature", "bin", "default_left")}
+            pos = ops.advance_rows(binned, pos, split, *self._children(split, ids),
+                                   first_node=first)
+        return pos
+
+    def leaves(self, csr) -> torch.Tensor:
+        """int32 ``[rows, trees]``: the heap id of the node every row of ``csr``
+        ends on in every tree (:func:`~dmlc_core_amd.ops.predict_forest`) --
+        the categorical features of a GBDT-to-linear stack."""
+        self._device_csr(csr)
+        if self.cuts is None:
+            raise ValueError("SparseGBDT.leaves: the model has no cuts (fit or boost first)")
+        return ops.predict_forest(csr, self._forest(), "leaf")
 
 
 _FM_LOSSES = {"logistic": 0, "squared": 1}

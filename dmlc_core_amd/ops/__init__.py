@@ -3,10 +3,12 @@
 Every op launches a hand-written CDNA4 kernel from ``libdmlc.so`` on the
 current torch stream (src/gpu/feature_kernels.hip, spmm_kernels.hip,
 transpose_kernels.hip, gather_kernels.hip, ffm_kernels.hip, rank_kernels.hip,
-compact_kernels.hip, optim_kernels.hip, gbdt_kernels.hip).
+compact_kernels.hip, optim_kernels.hip, gbdt_kernels.hip, forest_kernels.hip).
 Histogram gradient-boosted trees run on the column-major binned matrix:
 :func:`feature_cuts` -> :func:`bin_features` once, then per tree level
 :func:`grad_histogram` -> :func:`best_splits` -> :func:`advance_rows`.
+The trained forest scores row-major batches in one launch:
+:func:`pack_forest` once, then :func:`predict_forest` for margins or leaf ids.
 There is no PyTorch fallback: on a machine without the extension or a GPU these
 functions raise.
 
@@ -29,7 +31,7 @@ __all__ = ["spmv", "spmv_t", "hashed_dense", "SpMVFunction", "csr_spmv", "transp
            "ffm", "ffm_t", "FFMFunction", "csr_ffm",
            "qid_groups", "group_rows", "rank_loss", "rank_loss_parts", "RankLossFunction", "ndcg",
            "feature_cuts", "bin_features", "gradient_scale", "grad_histogram", "best_splits",
-           "advance_rows"]
+           "advance_rows", "pack_forest", "predict_forest"]
 
 # persistent transpose scratch per (device, stream), grow-only: a rebuild (a
 # further shard, a refreshed batch) allocates no multi-GB scratch again
@@ -1487,4 +1489,130 @@ def advance_rows(binned: Dict, pos: torch.Tensor, split: Dict, left: torch.Tenso
         _dmlc.gbdt_advance(arg, _ptr(pos), _ptr(feature), _ptr(split["bin"]),
                            _ptr(split["default_left"]), _ptr(left), _ptr(right), first_node, n,
                            _ptr(out), _stream())
+    return out
+
+
+# ------------------------------------------------- forest inference (GB6)
+def pack_forest(trees, cuts: Dict) -> Dict:
+    """``SparseGBDT.trees`` and ``cuts`` as one device tensor for
+    :func:`predict_forest`: ``{"node": int32 [T, size, 2], "trees": T, "size",
+    "depth"}``, every tree a heap of ``size = 2**(depth + 1) - 1`` nodes of 8
+    bytes.  Word 0 is ``feature | default_left << 31`` for an internal node and
+    -1 for a leaf (``feature < 0``, and every node of the last level); word 1
+    holds the bits of the float threshold ``cut[cut_ptr[feature] + bin]`` --
+    ``+inf`` when ``bin`` is the feature's last -- or of ``leaf``.
+
+    ``x <= threshold`` is exactly ``bin_features(x) <= bin``: cuts ascend
+    strictly, so ``#cuts < x <= b`` means ``x <= cut[b]``, and the cap at the
+    last bin sends every present value left.  Torch plumbing, no kernel; one
+    device-to-host read (the checks).  Raises ``ValueError`` for trees of
+    unequal size, a size that is not ``2**k - 1`` with depth ``k - 1`` in
+    [1, 14], a split on a feature without cuts, or a ``bin`` outside its
+    feature's cuts.  No trees give ``T = 0``."""
+    cut_ptr, cut = cuts.get("cut_ptr"), cuts.get("cut")
+    nfeat = cut_ptr.numel() - 1 if isinstance(cut_ptr, torch.Tensor) else -1
+    dev = cut.device if isinstance(cut, torch.Tensor) else None
+    _check_cuts("pack_forest", cuts, nfeat, dev)
+    trees = list(trees)
+    if not trees:
+        return {"node": torch.empty((0, 0, 2), dtype=torch.int32, device=dev), "trees": 0,
+                "size": 0, "depth": 0}
+    size = int(trees[0]["feature"].numel())
+    for tree in trees:
+        for k, dt in (("feature", torch.int64), ("bin", torch.int32), ("default_left", torch.bool),
+                      ("leaf", torch.float32)):
+            t = tree.get(k)
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1 or t.device != dev:
+                raise ValueError(f"pack_forest: a tree's {k!r} must be a 1-D {dt} tensor on {dev}")
+            if t.numel() != size:
+                raise ValueError(f"pack_forest: trees of unequal size ({t.numel()} and {size} "
+                                 "nodes)")
+    depth = (size + 1).bit_length() - 2
+    if size != 2 ** (depth + 1) - 1 or not 1 <= depth <= 14:
+        raise ValueError(f"pack_forest: a tree has {size} nodes, not 2**(depth + 1) - 1 with depth "
+                         "in [1, 14]")
+    feature, tbin, left, leaf = (torch.stack([t[k] for t in trees])
+                                 for k in ("feature", "bin", "default_left", "leaf"))
+    inner = feature >= 0
+    inner[:, size // 2:] = False  # the last level has no children
+    known = inner & (feature < nfeat)
+    f = torch.where(known, feature, torch.zeros_like(feature))
+    if nfeat > 0:
+        first, ncuts = cut_ptr[f], cut_ptr[f + 1] - cut_ptr[f]
+    else:
+        first, ncuts = torch.zeros_like(f), torch.zeros_like(f)
+    no_cuts = inner & (~known | (ncuts < 1) | (feature >= (1 << 28)))
+    bad_bin = inner & ~no_cuts & ((tbin < 0) | (tbin >= ncuts))
+    flags = torch.stack([no_cuts.any(), bad_bin.any()]).tolist()
+    if flags[0]:
+        raise ValueError("pack_forest: a node splits on a feature without cuts")
+    if flags[1]:
+        raise ValueError("pack_forest: a node's bin is outside its feature's cuts")
+    if cut.numel() > 0:
+        at = torch.where(inner, first + tbin, torch.zeros_like(first))
+        thr = cut[at.clamp_(0, cut.numel() - 1)]  # a cut_ptr that overruns cut forms no address
+    else:
+        thr = torch.zeros_like(leaf)
+    thr = torch.where(tbin == ncuts - 1, torch.full_like(thr, float("inf")), thr)
+    word0 = torch.where(inner, torch.where(left, f - (1 << 31), f), torch.full_like(f, -1))
+    word1 = torch.where(inner, thr, leaf).view(torch.int32)
+    node = torch.stack([word0.to(torch.int32), word1], 2).contiguous()
+    return {"node": node, "trees": len(trees), "size": size, "depth": depth}
+
+
+def predict_forest(csr: Dict, forest: Dict, output: str = "margin",
+                   validate: bool = True) -> torch.Tensor:
+    """Every row of a device CSR walked down every tree of a packed forest in
+    one launch (GB6, src/gpu/forest_kernels.hip), in row order, with neither a
+    transpose nor bins.  ``output="margin"``: float32 ``[rows]``, ``((0 +
+    leaf_0) + leaf_1) + ...`` in f32 in tree order -- the bytes of
+    ``SparseGBDT.predict``'s level-by-level path.  ``output="leaf"``: int32
+    ``[rows, T]``, the heap id of the node each row ends on in each tree.
+
+    At a node an entry of the split feature goes left when ``value <=
+    threshold``; a row without one takes the node's default side; ids that no
+    tree splits on (any id, also ``>= num_features``) are ignored, and a row's
+    ids are taken to be distinct.  ``csr``: the shapes of :func:`spmv` (32- or
+    64-bit indices, ``value`` optional (1.0), ``offset`` may be a row slice); a
+    transpose's pair views are unpaired into contiguous copies first.
+    ``forest``: :func:`pack_forest`'s dict on the CSR's device.  Anything else
+    raises ``ValueError`` before a launch.
+
+    One wave owns a row and stages it once in LDS (rows longer than
+    ``_dmlc.forest_staged_row_entries()`` are re-staged in chunks per level);
+    its lanes walk ``_dmlc.forest_trees_per_pass()`` trees at a time.  No
+    atomics: the same inputs give the same bytes.  A NaN value is flagged on
+    the device: ``validate=True`` reads the flag word -- the call's one
+    device-to-host read -- and raises ``ValueError``; ``validate=False`` reads
+    nothing and the NaN entry goes right.  No rows or no trees give zeros (an
+    empty ``[rows, 0]`` for leaves) without a launch."""
+    if output not in ("margin", "leaf"):
+        raise ValueError(f"predict_forest: output must be 'margin' or 'leaf', got {output!r}")
+    node = forest.get("node") if isinstance(forest, dict) else None
+    if not isinstance(node, torch.Tensor) or node.dtype != torch.int32 or node.dim() != 3 \
+            or node.shape[2] != 2 or not node.is_contiguous():
+        raise ValueError("predict_forest: forest must be pack_forest's dict (node: int32 "
+                         "[T, size, 2])")
+    ntrees, size, depth = int(node.shape[0]), int(node.shape[1]), int(forest.get("depth", 0))
+    if ntrees > 0 and (not 1 <= depth <= 14 or size != 2 ** (depth + 1) - 1):
+        raise ValueError("predict_forest: forest['depth'] does not fit the node tensor")
+    csr = _unpair(csr)
+    view, rows = _view(csr)
+    _check_device("forest['node']", node, csr)
+    if csr.get("value") is not None and csr["value"].numel() != csr["index"].numel():
+        raise ValueError(f"csr['value'] has {csr['value'].numel()} entries, "
+                         f"csr['index'] {csr['index'].numel()}")
+    dev = node.device
+    if output == "margin":
+        out = torch.zeros(rows, dtype=torch.float32, device=dev)
+    else:
+        out = torch.zeros((rows, ntrees), dtype=torch.int32, device=dev)
+    if rows == 0 or ntrees == 0:
+        return out
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    _dmlc.forest_predict(view, _ptr(node), ntrees, size, depth,
+                         _ptr(out) if output == "margin" else 0,
+                         _ptr(out) if output == "leaf" else 0, _ptr(err), _stream())
+    if validate and int(err.item()):
+        raise ValueError("predict_forest: a value is NaN")
     return out

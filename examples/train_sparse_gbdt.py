@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """End-to-end demonstrator: LibSVM -> GPU parser -> CSR resident in HBM ->
 quantile cuts and the column-major binned matrix (once) -> histogram
-gradient-boosted trees (HIP kernels GB1 - GB5), one process on one MI355X.
+gradient-boosted trees (HIP kernels GB1 - GB5) on the first 90 % of the rows;
+the rest is held out and scored in row order by the fused forest kernel (GB6,
+predict(method="rows")), one process on one MI355X.
 
     python examples/train_sparse_gbdt.py data/train.libsvm --rounds 20 --max-depth 6
 
@@ -44,7 +46,13 @@ def main():
     torch.cuda.synchronize()
     t_parse = time.perf_counter() - t0
     num_features = int(csr.max_index) + 1
-    t = data.csr_to_torch(csr)
+    whole = data.csr_to_torch(csr)
+    ntrain = max(int(csr.rows) * 9 // 10, 1)
+    t = dict(whole, offset=whole["offset"][:ntrain + 1])  # row slices of the same arrays
+    held = dict(whole, offset=whole["offset"][ntrain:])
+    for k in ("label", "weight"):
+        if whole.get(k) is not None:
+            t[k], held[k] = whole[k][:ntrain], whole[k][ntrain:]
     label = t["label"].float()
     model = SparseGBDT(num_features, max_bins=args.max_bins, max_depth=args.max_depth,
                        learning_rate=args.lr, objective=args.objective)
@@ -62,11 +70,17 @@ def main():
     torch.cuda.synchronize()
     t_boost = time.perf_counter() - t0
     splits = sum(int((tree["feature"] >= 0).sum()) for tree in model.trees)
+    held_loss = None
+    if held["offset"].numel() > 1:
+        held_loss = round(float(model.loss(model.predict(held, method="rows"),
+                                           held["label"].float(), held.get("weight"))), 5)
     print(json.dumps({"rows": int(csr.rows), "nnz": int(csr.nnz), "num_features": num_features,
                       "total_bins": int(model.cuts["cut"].numel()),
                       "parse_sec": round(t_parse, 4), "cuts_and_bins_sec": round(t_bin, 4),
                       "boost_sec_per_round": round(t_boost / max(args.rounds, 1), 4),
-                      "splits": splits, "loss_per_round": [round(x, 5) for x in history]}),
+                      "splits": splits, "held_out_rows": int(csr.rows) - ntrain,
+                      "held_out_loss": held_loss,
+                      "loss_per_round": [round(x, 5) for x in history]}),
           flush=True)
 
 

@@ -24,6 +24,12 @@ cuts for each of 1 M features 64 nodes would need 262 GB.
   advance    ops.advance_rows with those splits, per call over windows of 50
              calls back to back (a single call is mostly launch and synchronise)
   boost      one depth-6 SparseGBDT.boost (logistic)
+  predict    8 depth-6 trees over the shard: SparseGBDT.predict(method="levels")
+             (bin_features on the cached transpose, then a GB5 launch per tree
+             and level) against method="rows" (GB6, one launch, the packed forest
+             cached) and ops.pack_forest alone.  The two margin vectors must be
+             equal bit for bit.  `rows_share`: the time one pass over the CSR's
+             bytes takes at the measured device copy rate, over the measured time
 
 Every figure is the median (and the fastest) of --iters host-clock windows
 around one call each, ending in a device synchronise, after one warm-up call.
@@ -256,6 +262,27 @@ def main():
     # -------------------------------------------------------------------- boost
     model = SparseGBDT(feats, max_bins=args.max_bins, max_depth=6)
     note("boost_depth6", timed(lambda: model.boost(binned, csr["label"]), 2))
+
+    # ------------------------------------------------------------------ predict
+    while len(model.trees) < 8:
+        model.boost(binned, csr["label"])
+    del model.trees[8:]
+    del binned
+    torch.cuda.empty_cache()
+    note("predict_levels_8", timed(lambda: model.predict(csr), 3))
+    csr.pop("transpose", None)  # the levels path's, cached by its first call
+    ops.release_workspace()
+    torch.cuda.empty_cache()
+    note("pack_forest_8", timed(lambda: ops.pack_forest(model.trees, model.cuts)))
+    r = timed(lambda: model.predict(csr, method="rows"))
+    csr_bytes = sum(csr[k].numel() * csr[k].element_size() for k in ("offset", "index", "value")
+                    if csr.get(k) is not None)
+    r["rows_share"] = round(csr_bytes / (res["copy_gb_s"] * 1e6) / r["ms"], 3)
+    note("predict_rows_8", r)
+    res["levels_over_rows"] = ratio(res["predict_levels_8"], r)
+    res["predict_trees_with_splits"] = sum(int(t["feature"][0]) >= 0 for t in model.trees)
+    assert torch.equal(model.predict(csr, method="rows"), model.predict(csr)), \
+        "predict: the rows path and the levels path differ"
     print(json.dumps(res), flush=True)
 
 

@@ -39,7 +39,8 @@
  *   GB3 grad histogram   LaunchGbdtHistogram      (gbdt_kernels.hip)
  *   GB4 best splits      LaunchGbdtBestSplits     (gbdt_kernels.hip)
  *   GB5 advance rows     LaunchGbdtAdvance        (gbdt_kernels.hip)
- * The launchers of K9, K11, M1 / M2, FF1 / FF2, G2 and the transpose take
+ *   GB6 forest inference LaunchForestPredict      (forest_kernels.hip)
+ * The launchers of K9, K11, M1 / M2, FF1 / FF2, G2, GB6 and the transpose take
  * their CSR operand as one CsrView and pick the kernel for its index width
  * (and pair layout) themselves; launch_common.h holds what they share.
  * All launchers are asynchronous on `stream` and never allocate or
@@ -802,6 +803,36 @@ void LaunchGbdtAdvance(const GbdtBinned& m, const int32_t* pos_in, const int64_t
                        const int32_t* split_bin, const uint8_t* default_left, const int32_t* left,
                        const int32_t* right, int32_t first_node, uint32_t num_nodes, int32_t* pos_out,
                        hipStream_t stream);
+// ---------------- forest inference on the row CSR (forest_kernels.hip) ----------------
+/*! \brief entries of a row GB6 stages in a wave's LDS slice (8 bytes each); a
+ *  longer row is re-staged in chunks of this many at every tree level */
+constexpr uint32_t kForestRowEntries = 1024;
+/*! \brief trees GB6 walks at once: one per lane of the wave that owns the row */
+constexpr uint32_t kForestTreesPerPass = 64;
+/*!
+ * \brief a packed forest: node int32 [trees x size x 2], heap layout (children
+ *  of i: 2i + 1, 2i + 2), size = 2^(depth + 1) - 1, depth 1 .. 14.  Word 0 of a
+ *  node: feature (< 2^28) | default_left << 31, or -1 for a leaf; word 1: the
+ *  bits of the float threshold (go left when x <= it) or of the leaf value.
+ */
+struct ForestView {
+  const int32_t* node;  // 8-byte aligned
+  uint32_t trees, size, depth;
+};
+/*!
+ * \brief GB6: walk every row of `csr` (the CSR shapes of K11: value may be
+ *  nullptr, offset may be a slice, 32- or 64-bit indices, no pairs) down every
+ *  tree: an entry of the node's feature goes left when value <= threshold, a
+ *  row without one to the default side, at most `depth` steps.  margin (may be
+ *  null) [nrows] = ((0 + leaf_0) + leaf_1) + ... in f32 in tree order; leaf
+ *  (may be null) int32 [nrows x trees] = the heap id of the node the row ends
+ *  on.  An id matches a feature only as a whole 64-bit number; ids that are no
+ *  split feature are ignored.  A NaN value ORs kGbdtErrNaN into *error (a device
+ *  word the caller zeroed) and goes right.  No atomics on the outputs; nrows ==
+ *  0 or trees == 0 returns before any HIP call.
+ */
+void LaunchForestPredict(const CsrView& csr, const ForestView& forest, float* margin, int32_t* leaf,
+                         uint32_t* error, hipStream_t stream);
 /*! \brief fill n floats with v */
 void LaunchFill(float* p, size_t n, float v, hipStream_t stream);
 /*!

@@ -1290,6 +1290,21 @@ PYBIND11_MODULE(_dmlc, m) {
       py::arg("default_left"), py::arg("left"), py::arg("right"), py::arg("first_node"),
       py::arg("num_nodes"), py::arg("pos_out"), py::arg("stream"));
   m.def(
+      "forest_predict",
+      [stream_of](const CsrArg& csr, uintptr_t node, uint32_t trees, uint32_t size, uint32_t depth,
+                  uintptr_t margin, uintptr_t leaf, uintptr_t error, uintptr_t stream) {
+        gpu::LaunchForestPredict(View(csr),
+                                 gpu::ForestView{Ptr<const int32_t>(node), trees, size, depth},
+                                 Ptr<float>(margin), Ptr<int32_t>(leaf), Ptr<uint32_t>(error),
+                                 stream_of(stream));
+      },
+      py::arg("csr"), py::arg("node"), py::arg("trees"), py::arg("size"), py::arg("depth"),
+      py::arg("margin"), py::arg("leaf"), py::arg("error"), py::arg("stream"));
+  m.def("forest_staged_row_entries", []() { return gpu::kForestRowEntries; },
+        "entries of a row GB6 stages in LDS; a longer row is re-staged in chunks per level");
+  m.def("forest_trees_per_pass", []() { return gpu::kForestTreesPerPass; },
+        "trees GB6 walks at once, one per lane");
+  m.def(
       "lazy_update",
       [stream_of](int rule, uintptr_t param, uintptr_t ids, uintptr_t grad, uintptr_t state0,
                   uintptr_t state1, uint64_t features, uint64_t nrows, uint64_t width, float a,
