@@ -59,6 +59,9 @@ $(BUILD)/obj/%.hip.o: src/%.hip $(HEADERS)
 # bit: the compiler may not select packed f32 ops (v_pk_add/mul/fma_f32) in that file.  A
 # guard, not a tuning knob: see the header of forest_kernels.hip and profiles/gbdt/README.md
 $(BUILD)/obj/gpu/forest_kernels.hip.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+# RK1 / RK2: the boost mode's gradient must equal the loss mode's bit for bit, from two
+# instantiations of one template -- the same guard, for the whole file (its header)
+$(BUILD)/obj/gpu/rank_kernels.hip.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 $(LIB): $(CPU_OBJS) $(HIP_OBJS)
 	@mkdir -p $(LIBDIR)

@@ -238,8 +238,8 @@ def _group_ptr(csr) -> torch.Tensor:
         return ptr
     qid = csr.get("qid")
     if not isinstance(qid, torch.Tensor):
-        raise ValueError("SparseRanker: csr has neither 'group_ptr' nor a 'qid' tensor "
-                         "(parse a LibSVM file with qid: tokens)")
+        raise ValueError("a ranking model needs query groups: csr has neither 'group_ptr' nor "
+                         "a 'qid' tensor (parse a LibSVM file with qid: tokens)")
     key = (int(qid.data_ptr()), qid.numel(), qid._version)
     cached = csr.get("_group_ptr")
     if cached is None or cached[0] != key:
@@ -418,13 +418,32 @@ class SparseGBDT:
     outside every deeper window.  Objectives: ``"logistic"`` (labels in
     [0, 1], margins are logits) and ``"squared"``; margins start at 0.
     Gradients are summed as 64-bit fixed point, so a run is reproducible bit
-    for bit."""
+    for bit.
+
+    Ranking (LambdaMART): ``"rank:ndcg"`` and ``"rank:pairwise"`` boost on the
+    per-row gradients and hessians of the pairwise objective over the query
+    groups (:func:`~dmlc_core_amd.ops.rank_grad_hess`, ``weighting="ndcg"`` /
+    ``"none"``, with ``rank_sigma`` and ``rank_normalize``; ``"none"`` keeps
+    hessians at the scale at which ``min_child_weight=1`` and ``reg_lambda=1``
+    behave as they do for XGBoost).  Labels are relevance grades in [0, 31],
+    margins are scores; a row without a pair has g = h = 0 and only follows the
+    splits.  Row weights are refused, not ignored.  :meth:`fit` takes the
+    groups from ``csr["group_ptr"]`` or the runs of ``csr["qid"]``."""
+
+    _RANK_WEIGHTING = {"rank:ndcg": "ndcg", "rank:pairwise": "none"}
 
     def __init__(self, num_features: int, max_bins: int = 256, max_depth: int = 6,
                  learning_rate: float = 0.3, reg_lambda: float = 1.0, gamma: float = 0.0,
-                 min_child_weight: float = 1.0, objective: str = "logistic"):
-        if objective not in ("logistic", "squared"):
-            raise ValueError(f"objective must be 'logistic' or 'squared', got {objective!r}")
+                 min_child_weight: float = 1.0, objective: str = "logistic",
+                 rank_sigma: float = 1.0, rank_normalize: str = "none"):
+        if objective not in ("logistic", "squared") + tuple(self._RANK_WEIGHTING):
+            raise ValueError("objective must be 'logistic', 'squared', 'rank:ndcg' or "
+                             f"'rank:pairwise', got {objective!r}")
+        if isinstance(rank_sigma, bool) or not isinstance(rank_sigma, (int, float)) \
+                or not rank_sigma > 0:
+            raise ValueError(f"rank_sigma must be a number > 0, got {rank_sigma!r}")
+        if rank_normalize not in ("pairs", "none"):
+            raise ValueError(f"rank_normalize must be 'pairs' or 'none', got {rank_normalize!r}")
         if not 1 <= int(max_depth) <= 14:
             raise ValueError(f"max_depth must be in [1, 14], got {max_depth!r}")
         if not float(reg_lambda) > 0:
@@ -433,6 +452,7 @@ class SparseGBDT:
         self.max_depth, self.learning_rate = int(max_depth), float(learning_rate)
         self.reg_lambda, self.gamma = float(reg_lambda), float(gamma)
         self.min_child_weight, self.objective = float(min_child_weight), objective
+        self.rank_sigma, self.rank_normalize = float(rank_sigma), rank_normalize
         self.cuts = None    # feature_cuts of the training data
         self.trees = []     # dicts of feature / bin / default_left / leaf
         self.margin = None  # the training rows' margins, updated by boost()
@@ -443,7 +463,24 @@ class SparseGBDT:
         if not csr["index"].is_cuda:
             raise ValueError("SparseGBDT runs on a device CSR (csr_to_torch of a GPU parse)")
 
-    def _gradients(self, margin, label, weight):
+    def _rank_groups(self, what: str, weight, group_ptr):
+        """the ``weighting`` of a rank objective, its operands checked; None for the others"""
+        weighting = self._RANK_WEIGHTING.get(self.objective)
+        if weighting is None:
+            return None
+        if weight is not None:
+            raise ValueError(f"SparseGBDT.{what}: objective {self.objective!r} takes no row "
+                             "weights (the rank kernels do not use them)")
+        if group_ptr is None:
+            raise ValueError(f"SparseGBDT.{what}: objective {self.objective!r} needs group_ptr, "
+                             "the query groups of the rows")
+        return weighting
+
+    def _gradients(self, margin, label, weight, group_ptr=None):
+        weighting = self._RANK_WEIGHTING.get(self.objective)
+        if weighting is not None:  # boost() has checked weight and group_ptr
+            return ops.rank_grad_hess(margin, label, group_ptr, weighting, self.rank_sigma,
+                                      self.rank_normalize)
         if self.objective == "logistic":
             p = torch.sigmoid(margin)
             g, h = p - label, p * (1.0 - p)
@@ -453,25 +490,43 @@ class SparseGBDT:
             g, h = g * weight, h * weight
         return g.contiguous(), h.contiguous()
 
-    def loss(self, margin: torch.Tensor, label: torch.Tensor, weight=None) -> torch.Tensor:
-        """the objective's mean loss of ``margin`` (``mean(weight * loss)``)"""
+    def loss(self, margin: torch.Tensor, label: torch.Tensor, weight=None,
+             group_ptr=None) -> torch.Tensor:
+        """the objective's mean loss of ``margin`` (``mean(weight * loss)``; a
+        rank objective: :func:`~dmlc_core_amd.ops.rank_loss` over ``group_ptr``)"""
+        weighting = self._rank_groups("loss", weight, group_ptr)
+        if weighting is not None:
+            return rank_loss(margin, label, group_ptr, weighting, self.rank_sigma)
         return _fm_loss(margin, label, weight, self.objective)
+
+    @torch.no_grad()
+    def ndcg(self, csr, k: Optional[int] = 10, method: str = "rows") -> torch.Tensor:
+        """Mean NDCG@k over the query groups of ``csr`` (its ``group_ptr``, or the
+        runs of its ``qid``) of ``predict(csr, method)``; a group without a
+        relevant row counts 1.0"""
+        ptr = _group_ptr(csr)
+        return ndcg(self.predict(csr, method), csr["label"].float(), ptr, k).mean()
 
     def fit(self, csr, rounds: int) -> "SparseGBDT":
         """Cuts and bins of ``csr`` once, then ``rounds`` trees against
-        ``csr["label"]`` (row-weighted by ``csr["weight"]`` if present)."""
+        ``csr["label"]`` (row-weighted by ``csr["weight"]`` if present; a rank
+        objective: over ``csr["group_ptr"]`` or the runs of ``csr["qid"]``)."""
         self._device_csr(csr)
+        group_ptr = _group_ptr(csr) if self.objective in self._RANK_WEIGHTING else None
+        self._rank_groups("fit", csr.get("weight"), group_ptr)
         self.cuts = ops.feature_cuts(csr, self.num_features, self.max_bins)
         binned = ops.bin_features(csr, self.cuts, self.num_features)
         self.trees, self.margin, self._packed = [], None, None
         label, weight = csr["label"].float(), csr.get("weight")
         for _ in range(int(rounds)):
-            self.boost(binned, label, weight)
+            self.boost(binned, label, weight, group_ptr)
         return self
 
-    def boost(self, binned, label: torch.Tensor, weight=None) -> torch.Tensor:
+    def boost(self, binned, label: torch.Tensor, weight=None, group_ptr=None) -> torch.Tensor:
         """Grow one tree on ``binned`` and return the updated training margins
-        (kept in ``self.margin``; they start at 0)."""
+        (kept in ``self.margin``; they start at 0).  ``group_ptr``: the rows'
+        query groups, which a rank objective needs (and which take no ``weight``)."""
+        self._rank_groups("boost", weight, group_ptr)
         rows, dev = int(binned["rows"]), binned["row"].device
         if self.cuts is None:
             self.cuts = {"cut_ptr": binned["cut_ptr"], "cut": binned["cut"]}
@@ -482,7 +537,7 @@ class SparseGBDT:
                              f"{self.margin.numel()} training rows, binned has {rows}: the trees "
                              "were grown on another matrix (fit() starts a new model)")
         label = label.to(device=dev, dtype=torch.float32)
-        g, h = self._gradients(self.margin, label, weight)
+        g, h = self._gradients(self.margin, label, weight, group_ptr)
         scale = ops.gradient_scale(g, h)
         qgh = torch.stack([torch.round(g.double() * scale), torch.round(h.double() * scale)],
                           1).long()

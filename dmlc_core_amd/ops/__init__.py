@@ -9,6 +9,9 @@ Histogram gradient-boosted trees run on the column-major binned matrix:
 :func:`grad_histogram` -> :func:`best_splits` -> :func:`advance_rows`.
 The trained forest scores row-major batches in one launch:
 :func:`pack_forest` once, then :func:`predict_forest` for margins or leaf ids.
+Ranking on query groups: :func:`qid_groups`, then :func:`rank_loss` / :func:`ndcg`
+for a differentiable model, or :func:`rank_grad_hess` for the per-row gradients
+and hessians of a boosting round (LambdaMART).
 There is no PyTorch fallback: on a machine without the extension or a GPU these
 functions raise.
 
@@ -29,7 +32,8 @@ __all__ = ["spmv", "spmv_t", "hashed_dense", "SpMVFunction", "csr_spmv", "transp
            "compact_features", "lazy_update_",
            "spmm", "spmm_t", "SpMMFunction", "csr_spmm",
            "ffm", "ffm_t", "FFMFunction", "csr_ffm",
-           "qid_groups", "group_rows", "rank_loss", "rank_loss_parts", "RankLossFunction", "ndcg",
+           "qid_groups", "group_rows", "rank_loss", "rank_loss_parts", "rank_grad_hess",
+           "RankLossFunction", "ndcg",
            "feature_cuts", "bin_features", "gradient_scale", "grad_histogram", "best_splits",
            "advance_rows", "pack_forest", "predict_forest"]
 
@@ -898,6 +902,48 @@ def rank_loss_parts(score: torch.Tensor, label: torch.Tensor, group_ptr: torch.T
     if validate:
         _raise_rank_errors("rank_loss", err, rows)
     return loss_g, pairs_g, grad
+
+
+_RANK_NORMALIZE = ("pairs", "none")
+
+
+def rank_grad_hess(score: torch.Tensor, label: torch.Tensor, group_ptr: torch.Tensor,
+                   weighting: str = "ndcg", sigma: float = 1.0, normalize: str = "none",
+                   validate: bool = True):
+    """Every row's first and second derivative of the pairwise ranking
+    objective -- what a round of boosted trees needs (LambdaMART; RK1 / RK2 in
+    boost mode, src/gpu/rank_kernels.hip): ``(grad float32 [rows], hess float32
+    [rows])``.  With the pairs, ``x``, ``w`` and ``rho`` of
+    :func:`rank_loss_parts` (its operands, checks and ``weighting``)
+
+        grad[i] = c sigma   (- sum_{j: l_i > l_j} w_ij rho(x_ij) + sum_{j: l_j > l_i} w_ji rho(x_ji))
+        hess[i] = c sigma^2 sum_{j: l_j != l_i} w rho(x) (1 - rho(x))
+
+    where ``normalize="pairs"`` has ``c = 1 / |P|`` -- ``grad`` is then the
+    bytes of :func:`rank_loss_parts`' gradient -- and ``"none"`` has ``c = 1``,
+    the scale at which ``min_child_weight`` and ``reg_lambda`` of a tree
+    learner mean what they mean for XGBoost.  The hessian term is formed as
+    ``w e / (1 + e)^2`` from the pair's ``e = exp(-|x|)``: ``hess >= 0``, and a
+    saturated pair adds exactly 0.  Rows outside every group, rows of a group
+    without a pair and rows of a refused group get 0 in both.  No atomics, one
+    owner per row: the same inputs give the same bytes.  ``normalize`` other
+    than these two raises ``ValueError`` before a launch; ``validate`` as for
+    :func:`rank_loss_parts`."""
+    if normalize not in _RANK_NORMALIZE:
+        raise ValueError(f"rank_grad_hess: normalize must be one of {_RANK_NORMALIZE}, "
+                         f"got {normalize!r}")
+    rows, groups = _check_rank_loss(score, label, group_ptr, weighting, sigma)
+    dev = score.device
+    grad = torch.zeros(rows, dtype=torch.float32, device=dev)
+    hess = torch.zeros(rows, dtype=torch.float32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    weighted = weighting == "ndcg"
+    scratch = _workspace(4 * rows, dev) if weighted else None
+    _dmlc.rank_boost(_ptr(score), _ptr(label), _ptr(group_ptr), groups, rows, weighted, float(sigma),
+                     normalize == "pairs", _ptr(scratch), _ptr(grad), _ptr(hess), _ptr(err), _stream())
+    if validate:
+        _raise_rank_errors("rank_grad_hess", err, rows)
+    return grad, hess
 
 
 class RankLossFunction(torch.autograd.Function):

@@ -24,7 +24,7 @@
  *   FF2 ffm backward     LaunchFFMBackward        (ffm_kernels.hip)
  *   Q1 qid run flags     LaunchQidFlags           (rank_kernels.hip)
  *   Q2 qid group pointer LaunchQidGroupPtr        (rank_kernels.hip)
- *   RK1 rank, wave/group LaunchRankLoss, LaunchRankNdcg (rank_kernels.hip)
+ *   RK1 rank, wave/group LaunchRankLoss, LaunchRankNdcg, LaunchRankBoost (rank_kernels.hip)
  *   RK2 rank, block/group the same launchers, groups above kRankWaveGroupRows
  *   G1 row gather count  LaunchCSRGatherCount     (gather_kernels.hip)
  *   G2 row gather fill   LaunchCSRGatherFill      (gather_kernels.hip)
@@ -544,6 +544,23 @@ void LaunchRankLoss(const float* score, const float* label, const uint64_t* grou
  */
 void LaunchRankNdcg(const float* score, const float* label, const uint64_t* group_ptr, size_t groups,
                     uint64_t rows, uint32_t k, float* ndcg, int* error, hipStream_t stream);
+/*!
+ * \brief RK1 + RK2 in boost mode (LambdaMART): every row's first and second
+ *  derivative of the pairwise objective, for a round of boosted trees.  With
+ *  LaunchRankLoss' pairs, x, w and rho, and c = 1 / |P_g| (normalize_pairs) or 1,
+ *    grad[i] = c sigma   (- sum_{j: l_i > l_j} w rho(x_ij) + sum_{j: l_j > l_i} w rho(x_ji))
+ *    hess[i] = c sigma^2 sum_{j: l_j != l_i} w rho(x) (1 - rho(x))
+ *  with the hessian term formed as w e / (1 + e)^2 from the pair's e =
+ *  exp(-|x|): >= 0, and exactly 0 for a saturated pair.  grad is built by the
+ *  operations of LaunchRankLoss: with normalize_pairs it has that gradient's
+ *  bytes.  grad and hess [rows] must be zeroed by the caller (rows outside
+ *  every group, and rows of a refused group, keep 0); no per-group output.
+ *  row_scratch, error, NaN scores, determinism and groups == 0 as for
+ *  LaunchRankLoss.
+ */
+void LaunchRankBoost(const float* score, const float* label, const uint64_t* group_ptr, size_t groups,
+                     uint64_t rows, bool ndcg_weights, float sigma, bool normalize_pairs,
+                     float* row_scratch, float* grad, float* hess, int* error, hipStream_t stream);
 // ------------------------ HashedFM (fm_kernels.hip) ------------------------
 /*! \brief factor rank of the HIP HashedFM kernels and the [w | V] column count */
 constexpr int kFmRank = 16;

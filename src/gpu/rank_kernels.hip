@@ -2,7 +2,8 @@
  * \file src/gpu/rank_kernels.hip
  * \brief Q1 / Q2: runs of equal qid to a group pointer; RK1 / RK2: the pairwise
  *  ranking loss (RankNet / LambdaRank) of every query group with its gradient,
- *  and NDCG@k, over a score vector (f32).
+ *  NDCG@k, and (boost mode) every row's first and second derivative of the
+ *  pairwise objective for a round of boosted trees, over a score vector (f32).
  *
  * Q1   flag[r] = r == 0 || qid[r] != qid[r - 1]                     k_qid_flags
  * K3   LaunchScanU64: flag[r] becomes the number of run starts before r
@@ -20,6 +21,10 @@
  *   grad[i] = sigma/|P| (- sum_{j: l_i > l_j} w_ij rho(x_ij) + sum_{j: l_j > l_i} w_ji rho(x_ji))
  * (rho(z) = 1 / (1 + e^z); w is a constant of the gradient), and
  *   NDCG@k  = sum_{r_i < k} G_i D(r_i) / sum_{q_i < k} G_i D(q_i), 1 if the latter is 0.
+ * Boost mode (LambdaMART) writes no loss; with c = 1/|P| or 1 (PairParams::per_pair)
+ *   grad[i] = c sigma (the sum above)
+ *   hess[i] = c sigma^2 sum_{j: l_j != l_i} w rho(x) (1 - rho(x)),  x, w of the pair {i, j}
+ * rho (1 - rho) is even in x: a pair adds the same hessian to both of its rows.
  *
  * No sort.  r_i and q_i are counts -- #{j : s_j > s_i or (s_j == s_i and j < i)}
  * -- taken by comparing row i with every staged row j (CountRanks, the one
@@ -31,14 +36,21 @@
  * j (PairTerm): every pair is evaluated twice, once from each side, which buys
  * a grad[i] that is written once, by one lane, in an order fixed by the group's
  * length alone -- the same inputs give the same bytes.  One exp serves a pair's
- * softplus and rho.  The loss and |P| are taken from the l_i > l_j side only.
+ * softplus and rho, and in boost mode rho and the hessian term e / (1 + e)^2
+ * (never rho (1 - rho), which cancels where a pair saturates; a saturated pair
+ * has e = 0 and adds exactly 0).  hess[i] is a second sum next to grad[i]'s:
+ * the same owner, the same order, one more register per row (and one more LDS
+ * array in RK1, in the boost instantiation only).  grad is built by the very
+ * operations of the loss mode, so with c = 1/|P| it has the loss mode's bytes.
+ * The loss and |P| are taken from the l_i > l_j side only.
  * IDCG and the two NDCG sums are accumulated in f64 (their error would otherwise
  * enter every pair weight); everything else is f32.
  *
  * RK1 mapping.  The wave stages the group's (score, label, gain) in LDS once
  * (kRankWaveGroupRows rows x 20 bytes per wave with D(r_i) and the unscaled
- * gradient next to them).  Its 64 lanes are split into rows x slices: a group
- * of n rows gets lpr = 64 / next_pow2(n) lanes per row (1 from 33 rows up), lane
+ * gradient next to them; 24 in boost mode, with the unscaled hessian).  Its
+ * 64 lanes are split into rows x slices: a group of n rows gets
+ * lpr = 64 / next_pow2(n) lanes per row (1 from 33 rows up), lane
  * = row slot * lpr + slice, slice t sweeping j = t, t + lpr, ...; the slices of
  * a row are folded by __shfl_xor over distances lpr / 2 .. 1.  A 24-row group
  * (typical of the Yahoo set) thus keeps 48 lanes busy with 12 steps each where
@@ -61,9 +73,19 @@
  * group length is read back to size a launch.  A group whose pointers descend,
  * end past `rows` or span 2^31 rows or more forms no address, and a group with a
  * label that is negative, fractional, NaN or above kRankMaxLabel forms no pair:
- * both leave their rows of grad as the caller zeroed them, write loss 0 /
- * pairs 0 (NDCG 0) and OR kRankErrGroup / kRankErrLabel into the error word.
+ * both leave their rows of grad (and hess) as the caller zeroed them, write
+ * loss 0 / pairs 0 (NDCG 0; boost mode has no per-group output) and OR
+ * kRankErrGroup / kRankErrLabel into the error word.
  * All address arithmetic is size_t.
+ *
+ * Build.  This file is compiled with the target feature packed-fp32-ops turned
+ * off (Makefile, CMakeLists.txt), as forest_kernels.hip is: the boost mode's
+ * grad must be the loss mode's bytes out of another instantiation, and without
+ * the guard the compiler pairs the pair loop's f32 adds and products into
+ * v_pk_add_f32 / v_pk_mul_f32 differently in each (29 in RK1's loss
+ * instantiation, 14 in its boost one).  Every operation is the same IEEE
+ * operation either way; the guard leaves one instruction form to agree on.
+ * profiles/rank/README.md has both modes' times with and without it.
  */
 #include <dmlc/gpu/hip_utils.h>
 #include <dmlc/logging.h>
@@ -86,7 +108,7 @@ constexpr uint64_t kMaxGroupRows = 1ull << 31;
 static_assert(kTile == kThreads, "RK2 stages one tile row per thread");
 static_assert(kLabels <= dev::kWave, "RK2 keeps one label count per lane");
 
-enum class RankMode : int { kLoss = 0, kNdcg = 1 };
+enum class RankMode : int { kLoss = 0, kNdcg = 1, kBoost = 2 };
 
 // --------------------------------- Q1 / Q2 ---------------------------------
 __global__ __launch_bounds__(kThreads) void k_qid_flags(const uint64_t* __restrict__ qid, size_t rows,
@@ -154,6 +176,7 @@ __device__ __forceinline__ void NdcgTerms(float gain, uint32_t r, uint32_t q, ui
 struct PairParams {
   float sigma;
   bool ndcg;       // w_ij = |G_i - G_j| |D_i - D_j| / IDCG, else 1
+  bool per_pair;   // kBoost: c = 1 / |P|, else 1 (kLoss always divides by |P|)
   float inv_idcg;  // 1 / IDCG (0 if IDCG is 0: such a group has no pair)
 };
 
@@ -165,17 +188,24 @@ struct PairParams {
  *  overflow, and a saturated pair gives exactly 0 or 1.  Written without
  *  branches (an equal-label pair has weight 0 and adds +-0): the lanes of a
  *  wave rarely agree on the side, so a branch would run both anyway.
+ *  kBoost: no loss; from either side hacc += w rho (1 - rho) = w e / (1 + e)^2,
+ *  exactly 0 where e is.
  */
+template <RankMode kMode>
 __device__ __forceinline__ void PairTerm(const PairParams& p, float si, int li, float gi, float di,
                                          float sj, int lj, float gj, float dj, float* loss, float* acc,
-                                         uint32_t* pairs) {
+                                         float* hacc, uint32_t* pairs) {
   const bool upper = li > lj;
   const float x = p.sigma * (upper ? si - sj : sj - si);
   float w = li != lj ? 1.0f : 0.0f;
   if (p.ndcg) w *= fabsf(gi - gj) * fabsf(di - dj) * p.inv_idcg;
   const float e = expf(-fabsf(x));
   const float wrho = w * ((x > 0.0f ? e : 1.0f) / (1.0f + e));
-  *loss += upper ? w * (fmaxf(-x, 0.0f) + log1pf(e)) : 0.0f;
+  if (kMode == RankMode::kBoost) {
+    *hacc += w * e / ((1.0f + e) * (1.0f + e));
+  } else {
+    *loss += upper ? w * (fmaxf(-x, 0.0f) + log1pf(e)) : 0.0f;
+  }
   *acc += upper ? -wrho : wrho;
   *pairs += upper ? 1u : 0u;
 }
@@ -190,19 +220,29 @@ __device__ __forceinline__ bool GroupExtent(const uint64_t* __restrict__ ptr, si
   return ok;
 }
 
-/*! \brief what a kernel writes for a group: (loss, |P|) or NDCG */
+/*! \brief c sigma, the factor of a row's gradient sum: c = 1 / |P| (np; fp as f32), but 1
+ *  in kBoost without per_pair; 0 for a group without pairs, whose sums are +-0 */
+template <RankMode kMode>
+__device__ __forceinline__ float GradScale(const PairParams& p, bool any_pair, float fp) {
+  if (!any_pair) return 0.0f;
+  return (kMode == RankMode::kBoost && !p.per_pair) ? p.sigma : p.sigma / fp;
+}
+
+/*! \brief what a kernel writes for a group: (loss, |P|) or NDCG; kBoost: nothing */
 struct GroupOut {
   float* loss;     // kLoss: [groups]; kNdcg: the NDCG values
   int64_t* pairs;  // kLoss only
 };
 template <RankMode kMode>
 __device__ __forceinline__ void WriteGroup(const GroupOut& out, size_t g, float v, uint64_t pairs) {
+  if (kMode == RankMode::kBoost) return;
   out.loss[g] = v;
   if (kMode == RankMode::kLoss) out.pairs[g] = static_cast<int64_t>(pairs);
 }
 
 // ----------------------------------- RK1 -----------------------------------
 /*! \brief one wave's staged group */
+template <RankMode kMode>
 struct StagedGroup {
   float s[kCap];
   int l[kCap];
@@ -210,21 +250,27 @@ struct StagedGroup {
   float d[kCap];    // D(r_i)
   float acc[kCap];  // row i's unscaled gradient sum
 };
+/*! \brief kBoost alone pays the LDS of the second sum */
+template <>
+struct StagedGroup<RankMode::kBoost> : StagedGroup<RankMode::kLoss> {
+  float hacc[kCap];  // row i's unscaled hessian sum
+};
 
 /*!
  * \brief RK1.  The group loop is uniform over the wave and a wave's LDS image
  *  is written and read by its own lanes only: dev::wave_sync orders them.
- *  k: the NDCG cutoff (kNdcg).
+ *  k: the NDCG cutoff (kNdcg).  hess: kBoost's second output.
  */
 template <RankMode kMode>
 __global__ __launch_bounds__(kThreads) void k_rank_wave(
     const float* __restrict__ score, const float* __restrict__ label,
     const uint64_t* __restrict__ ptr, size_t groups, uint64_t rows, PairParams prm, uint32_t k,
-    float* __restrict__ grad, GroupOut out, int* __restrict__ error) {
-  __shared__ StagedGroup lds[kWaves];
+    float* __restrict__ grad, float* __restrict__ hess, GroupOut out, int* __restrict__ error) {
+  constexpr bool kBoost = kMode == RankMode::kBoost;
+  __shared__ StagedGroup<kMode> lds[kWaves];
   const uint32_t lane = threadIdx.x & (dev::kWave - 1);
   const uint32_t wave = dev::uniform(static_cast<uint32_t>(threadIdx.x / dev::kWave));
-  StagedGroup& s = lds[wave];
+  StagedGroup<kMode>& s = lds[wave];
   uint32_t err = 0;
   const size_t stride = static_cast<size_t>(gridDim.x) * kWaves;
   for (size_t g = static_cast<size_t>(blockIdx.x) * kWaves + wave; g < groups; g += stride) {
@@ -297,19 +343,23 @@ __global__ __launch_bounds__(kThreads) void k_rank_wave(
       for (uint32_t i0 = 0; i0 < n; i0 += slots) {
         const uint32_t i = i0 + slot;
         const bool live = i < n;
-        float acc = 0.0f;
+        float acc = 0.0f, hacc = 0.0f;
         if (live) {
           const float si = s.s[i], gi = s.gain[i], di = prm.ndcg ? s.d[i] : 0.0f;
           const int li = s.l[i];
           for (uint32_t j = slice; j < n; j += lpr) {
-            PairTerm(p, si, li, gi, di, s.s[j], s.l[j], s.gain[j], prm.ndcg ? s.d[j] : 0.0f, &loss,
-                     &acc, &pairs);
+            PairTerm<kMode>(p, si, li, gi, di, s.s[j], s.l[j], s.gain[j], prm.ndcg ? s.d[j] : 0.0f,
+                            &loss, &acc, &hacc, &pairs);
           }
         }
         for (uint32_t dist = lpr >> 1; dist >= 1u; dist >>= 1) {
           acc += __shfl_xor(acc, dist, dev::kWave);
+          if (kBoost) hacc += __shfl_xor(hacc, dist, dev::kWave);
         }
-        if (live && slice == 0u) s.acc[i] = acc;
+        if (live && slice == 0u) {
+          s.acc[i] = acc;
+          if constexpr (kBoost) s.hacc[i] = hacc;
+        }
       }
 #pragma unroll
       for (int dist = dev::kWave >> 1; dist >= 1; dist >>= 1) {
@@ -317,9 +367,12 @@ __global__ __launch_bounds__(kThreads) void k_rank_wave(
       }
       const uint32_t np = dev::wave_sum(pairs);
       const float fp = static_cast<float>(np);
-      const float scale = np != 0u ? prm.sigma / fp : 0.0f;
-      dev::wave_sync();  // acc[] is read by other lanes below
-      for (uint32_t i = lane; i < n; i += dev::kWave) grad[b + i] = scale * s.acc[i];
+      const float scale = GradScale<kMode>(prm, np != 0u, fp);
+      dev::wave_sync();  // acc[] (and hacc[]) is read by other lanes below
+      for (uint32_t i = lane; i < n; i += dev::kWave) {
+        grad[b + i] = scale * s.acc[i];
+        if constexpr (kBoost) hess[b + i] = scale * prm.sigma * s.hacc[i];
+      }
       if (lane == 0) WriteGroup<kMode>(out, g, np != 0u ? loss / fp : 0.0f, np);
     }
     dev::wave_sync();  // the next group's staging overwrites this one's
@@ -351,7 +404,9 @@ template <RankMode kMode>
 __global__ __launch_bounds__(kThreads) void k_rank_block(
     const float* __restrict__ score, const float* __restrict__ label,
     const uint64_t* __restrict__ ptr, size_t groups, uint64_t rows, PairParams prm, uint32_t k,
-    float* row_scratch, float* __restrict__ grad, GroupOut out, int* __restrict__ error) {
+    float* row_scratch, float* __restrict__ grad, float* __restrict__ hess, GroupOut out,
+    int* __restrict__ error) {
+  constexpr bool kBoost = kMode == RankMode::kBoost;
   __shared__ float ts[kTile];
   __shared__ int tl[kTile];
   __shared__ float tg[kTile];
@@ -437,7 +492,7 @@ __global__ __launch_bounds__(kThreads) void k_rank_block(
     const float idcg32 = static_cast<float>(idcg);
     p.inv_idcg = idcg32 > 0.0f ? 1.0f / idcg32 : 0.0f;
     const float fp = static_cast<float>(np);
-    const float scale = np != 0 ? prm.sigma / fp : 0.0f;
+    const float scale = GradScale<kMode>(prm, np != 0, fp);
     float loss = 0.0f;
     // the D(r_i) other threads left in row_scratch are read below after a barrier
     // (IDCG's BlockSum and the one that opens every tile)
@@ -448,7 +503,7 @@ __global__ __launch_bounds__(kThreads) void k_rank_block(
       const int li = live ? LabelOf(label[b + i]) : 0;
       const float gi = GainOf(li);
       const float di = (live && prm.ndcg) ? row_scratch[b + i] : 0.0f;
-      float acc = 0.0f;
+      float acc = 0.0f, hacc = 0.0f;
       uint32_t seen = 0;  // |P| comes from the label counts
       for (uint32_t j0 = 0; j0 < n; j0 += kTile) {
         __syncthreads();  // the tile's last readers are done
@@ -463,12 +518,16 @@ __global__ __launch_bounds__(kThreads) void k_rank_block(
         const uint32_t tn = n - j0 < kTile ? n - j0 : kTile;
         if (live) {
           for (uint32_t j = 0; j < tn; ++j) {
-            PairTerm(p, si, li, gi, di, ts[j], tl[j], tg[j], td[j], &loss, &acc, &seen);
+            PairTerm<kMode>(p, si, li, gi, di, ts[j], tl[j], tg[j], td[j], &loss, &acc, &hacc, &seen);
           }
         }
       }
-      if (live) grad[b + i] = scale * acc;
+      if (live) {
+        grad[b + i] = scale * acc;
+        if (kBoost) hess[b + i] = scale * prm.sigma * hacc;
+      }
     }
+    if (kBoost) continue;  // no per-group output
     loss = BlockSum(loss, sum32);
     if (t == 0) WriteGroup<kMode>(out, g, np != 0 ? loss / fp : 0.0f, np);
   }
@@ -478,11 +537,11 @@ __global__ __launch_bounds__(kThreads) void k_rank_block(
 template <RankMode kMode>
 void LaunchRank(const float* score, const float* label, const uint64_t* group_ptr, size_t groups,
                 uint64_t rows, const PairParams& prm, uint32_t k, float* row_scratch, float* grad,
-                const GroupOut& out, int* error, hipStream_t stream) {
+                float* hess, const GroupOut& out, int* error, hipStream_t stream) {
   hipLaunchKernelGGL(k_rank_wave<kMode>, dim3(GridFor(groups, kWaves)), dim3(kThreads), 0, stream,
-                     score, label, group_ptr, groups, rows, prm, k, grad, out, error);
+                     score, label, group_ptr, groups, rows, prm, k, grad, hess, out, error);
   hipLaunchKernelGGL(k_rank_block<kMode>, dim3(GridFor(groups, 1)), dim3(kThreads), 0, stream, score,
-                     label, group_ptr, groups, rows, prm, k, row_scratch, grad, out, error);
+                     label, group_ptr, groups, rows, prm, k, row_scratch, grad, hess, out, error);
   DMLC_HIP_CHECK_LAUNCH();
 }
 }  // namespace
@@ -513,16 +572,29 @@ void LaunchRankLoss(const float* score, const float* label, const uint64_t* grou
   CHECK(sigma > 0.0f) << "rank_loss: sigma must be > 0";
   CHECK(!ndcg_weights || row_scratch != nullptr) << "rank_loss: ndcg weights need the row scratch";
   LaunchRank<RankMode::kLoss>(score, label, group_ptr, groups, rows,
-                              PairParams{sigma, ndcg_weights, 0.0f}, 0u, row_scratch, grad,
-                              GroupOut{loss_g, pairs_g}, error, stream);
+                              PairParams{sigma, ndcg_weights, true, 0.0f}, 0u, row_scratch, grad,
+                              nullptr, GroupOut{loss_g, pairs_g}, error, stream);
+}
+
+void LaunchRankBoost(const float* score, const float* label, const uint64_t* group_ptr, size_t groups,
+                     uint64_t rows, bool ndcg_weights, float sigma, bool normalize_pairs,
+                     float* row_scratch, float* grad, float* hess, int* error, hipStream_t stream) {
+  if (groups == 0) return;
+  CHECK(sigma > 0.0f) << "rank_grad_hess: sigma must be > 0";
+  CHECK(!ndcg_weights || row_scratch != nullptr)
+      << "rank_grad_hess: ndcg weights need the row scratch";
+  LaunchRank<RankMode::kBoost>(score, label, group_ptr, groups, rows,
+                               PairParams{sigma, ndcg_weights, normalize_pairs, 0.0f}, 0u, row_scratch,
+                               grad, hess, GroupOut{nullptr, nullptr}, error, stream);
 }
 
 void LaunchRankNdcg(const float* score, const float* label, const uint64_t* group_ptr, size_t groups,
                     uint64_t rows, uint32_t k, float* ndcg, int* error, hipStream_t stream) {
   if (groups == 0) return;
   CHECK_GE(k, 1u) << "ndcg: k must be >= 1";
-  LaunchRank<RankMode::kNdcg>(score, label, group_ptr, groups, rows, PairParams{1.0f, false, 0.0f}, k,
-                              nullptr, nullptr, GroupOut{ndcg, nullptr}, error, stream);
+  LaunchRank<RankMode::kNdcg>(score, label, group_ptr, groups, rows,
+                              PairParams{1.0f, false, true, 0.0f}, k, nullptr, nullptr, nullptr,
+                              GroupOut{ndcg, nullptr}, error, stream);
 }
 
 }  // namespace gpu

@@ -1105,6 +1105,20 @@ PYBIND11_MODULE(_dmlc, m) {
       },
       py::arg("score"), py::arg("label"), py::arg("group_ptr"), py::arg("groups"), py::arg("rows"),
       py::arg("k"), py::arg("ndcg"), py::arg("error"), py::arg("stream"));
+  m.def(
+      "rank_boost",
+      [stream_of](uintptr_t score, uintptr_t label, uintptr_t group_ptr, size_t groups,
+                  uint64_t rows, bool ndcg_weights, float sigma, bool normalize_pairs,
+                  uintptr_t row_scratch, uintptr_t grad, uintptr_t hess, uintptr_t error,
+                  uintptr_t stream) {
+        gpu::LaunchRankBoost(Ptr<const float>(score), Ptr<const float>(label),
+                             Ptr<const uint64_t>(group_ptr), groups, rows, ndcg_weights, sigma,
+                             normalize_pairs, Ptr<float>(row_scratch), Ptr<float>(grad),
+                             Ptr<float>(hess), Ptr<int>(error), stream_of(stream));
+      },
+      py::arg("score"), py::arg("label"), py::arg("group_ptr"), py::arg("groups"), py::arg("rows"),
+      py::arg("ndcg_weights"), py::arg("sigma"), py::arg("normalize_pairs"), py::arg("row_scratch"),
+      py::arg("grad"), py::arg("hess"), py::arg("error"), py::arg("stream"));
   m.def("rank_wave_group_rows", []() { return gpu::kRankWaveGroupRows; },
         "rows of a group RK1 (one wave per group) takes; longer groups run on RK2");
   m.def("rank_tile_rows", []() { return gpu::kRankTileRows; },
