@@ -62,6 +62,8 @@ $(BUILD)/obj/gpu/forest_kernels.hip.o: HIPFLAGS += -Xclang -target-feature -Xcla
 # RK1 / RK2: the boost mode's gradient must equal the loss mode's bit for bit, from two
 # instantiations of one template -- the same guard, for the whole file (its header)
 $(BUILD)/obj/gpu/rank_kernels.hip.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+# SD2: a run's values are added one by one in input order -- the same guard
+$(BUILD)/obj/gpu/rowsort_kernels.hip.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 $(LIB): $(CPU_OBJS) $(HIP_OBJS)
 	@mkdir -p $(LIBDIR)

@@ -420,6 +420,14 @@ class SparseGBDT:
     Gradients are summed as 64-bit fixed point, so a run is reproducible bit
     for bit.
 
+    Precondition: no row repeats a feature id.  The reproducibility above and
+    the "same bytes" of :meth:`predict`'s two methods rest on it: a row with
+    two entries of a split feature on both sides of the cut is moved twice by
+    :func:`~dmlc_core_amd.ops.advance_rows` (the last writer wins) and counted
+    twice by :func:`~dmlc_core_amd.ops.grad_histogram`.
+    ``fit(..., check_rows=True)`` checks it;
+    ``ops.sort_rows(csr, duplicates="sum")`` repairs the data.
+
     Ranking (LambdaMART): ``"rank:ndcg"`` and ``"rank:pairwise"`` boost on the
     per-row gradients and hessians of the pairwise objective over the query
     groups (:func:`~dmlc_core_amd.ops.rank_grad_hess`, ``weighting="ndcg"`` /
@@ -507,13 +515,25 @@ class SparseGBDT:
         ptr = _group_ptr(csr)
         return ndcg(self.predict(csr, method), csr["label"].float(), ptr, k).mean()
 
-    def fit(self, csr, rounds: int) -> "SparseGBDT":
+    def fit(self, csr, rounds: int, check_rows: bool = False) -> "SparseGBDT":
         """Cuts and bins of ``csr`` once, then ``rounds`` trees against
         ``csr["label"]`` (row-weighted by ``csr["weight"]`` if present; a rank
-        objective: over ``csr["group_ptr"]`` or the runs of ``csr["qid"]``)."""
+        objective: over ``csr["group_ptr"]`` or the runs of ``csr["qid"]``).
+        ``check_rows``: raise ``ValueError`` when a row repeats a feature id,
+        or when the rows are not sorted by id (:func:`~dmlc_core_amd.ops.row_order`
+        counts repeats exactly only in sorted rows); one small launch and read."""
         self._device_csr(csr)
         group_ptr = _group_ptr(csr) if self.objective in self._RANK_WEIGHTING else None
         self._rank_groups("fit", csr.get("weight"), group_ptr)
+        if check_rows:
+            # by id alone: a field column is no part of a GBDT feature
+            order = ops.row_order({k: v for k, v in csr.items() if k != "field"})
+            if not order["sorted"] or order["duplicates"]:
+                what = (f"{order['duplicates']} entries repeat a feature id of their row"
+                        if order["sorted"] else "the rows are not sorted by feature id, so "
+                        "repeated ids cannot be ruled out")
+                raise ValueError(f"SparseGBDT.fit: {what}; canonicalise the data with "
+                                 "ops.sort_rows(csr, duplicates=\"sum\")")
         self.cuts = ops.feature_cuts(csr, self.num_features, self.max_bins)
         binned = ops.bin_features(csr, self.cuts, self.num_features)
         self.trees, self.margin, self._packed = [], None, None

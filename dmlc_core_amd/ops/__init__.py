@@ -3,7 +3,8 @@
 Every op launches a hand-written CDNA4 kernel from ``libdmlc.so`` on the
 current torch stream (src/gpu/feature_kernels.hip, spmm_kernels.hip,
 transpose_kernels.hip, gather_kernels.hip, ffm_kernels.hip, rank_kernels.hip,
-compact_kernels.hip, optim_kernels.hip, gbdt_kernels.hip, forest_kernels.hip).
+compact_kernels.hip, optim_kernels.hip, gbdt_kernels.hip, forest_kernels.hip,
+rowsort_kernels.hip).
 Histogram gradient-boosted trees run on the column-major binned matrix:
 :func:`feature_cuts` -> :func:`bin_features` once, then per tree level
 :func:`grad_histogram` -> :func:`best_splits` -> :func:`advance_rows`.
@@ -12,6 +13,8 @@ The trained forest scores row-major batches in one launch:
 Ranking on query groups: :func:`qid_groups`, then :func:`rank_loss` / :func:`ndcg`
 for a differentiable model, or :func:`rank_grad_hess` for the per-row gradients
 and hessians of a boosting round (LambdaMART).
+Canonical rows -- entries sorted by id or field, repeated ids merged -- come from
+:func:`sort_rows`; :func:`row_order` tells whether a CSR needs it.
 There is no PyTorch fallback: on a machine without the extension or a GPU these
 functions raise.
 
@@ -28,7 +31,7 @@ import torch
 from .. import _dmlc
 
 __all__ = ["spmv", "spmv_t", "hashed_dense", "SpMVFunction", "csr_spmv", "transpose",
-           "gather_rows", "gather_buffers", "release_workspace",
+           "gather_rows", "gather_buffers", "release_workspace", "sort_rows", "row_order",
            "compact_features", "lazy_update_",
            "spmm", "spmm_t", "SpMMFunction", "csr_spmm",
            "ffm", "ffm_t", "FFMFunction", "csr_ffm",
@@ -599,6 +602,146 @@ def gather_rows(csr: Dict, rows: torch.Tensor, out: Optional[Dict] = None) -> Di
         res[k] = bufs[k][:n_sel]
     res["_buffers"] = bufs
     return res
+
+
+def _sort_operand(name: str, csr: Dict, by: str):
+    """``csr`` as :func:`sort_rows` / :func:`row_order` take it, checked from
+    the cheapest mistake to the device: (csr unpaired, view, rows, entries)"""
+    if by not in ("index", "field"):
+        raise ValueError(f"{name}: by must be 'index' or 'field', got {by!r}")
+    csr = _unpair(csr)
+    offset, index, value, field = csr["offset"], csr["index"], csr.get("value"), csr.get("field")
+    if by == "field" and not isinstance(field, torch.Tensor):
+        raise ValueError(f"{name}: by='field' needs csr['field']")
+    if value is not None and value.dtype != torch.float32:
+        raise ValueError(f"{name}: csr['value'] must be float32")
+    if offset.element_size() != 8 or offset.numel() < 1 or index.dtype not in _INDEX_DTYPES:
+        raise ValueError(f"{name}: csr['offset'] must be a 64-bit row pointer of rows + 1 entries "
+                         "and csr['index'] a 32- or 64-bit integer tensor")
+    if isinstance(field, torch.Tensor) and field.dtype != index.dtype:
+        raise ValueError(f"{name}: csr['field'] must have index's dtype")
+    for k in ("offset", "index", "value", "field"):
+        t = csr.get(k)
+        if isinstance(t, torch.Tensor) and (not t.is_cuda or not t.is_contiguous() or t.dim() != 1):
+            raise ValueError(f"{name}: csr[{k!r}] must be a contiguous 1-D device tensor")
+    view, nrows = _view(csr)
+    entries = min(t.numel() for t in (index, value, field) if isinstance(t, torch.Tensor))
+    return csr, view, nrows, entries
+
+
+def _raise_sort_errors(name: str, err: int) -> None:
+    if err & _dmlc.sort_err_offset:
+        raise ValueError(f"{name}: csr['offset'] descends or points outside index / value / field")
+    if err & _dmlc.sort_err_row_length:
+        raise ValueError(f"{name}: a row has 2^32 entries or more")
+    if err:
+        raise ValueError(f"{name}: the kernels report error word {err}")
+
+
+def sort_rows(csr: Dict, by: str = "index", duplicates: str = "keep") -> Dict:
+    """The CSR with every row's entries in canonical order (scipy's
+    ``sort_indices`` / ``sum_duplicates``), by a segmented sort in HIP (SR0 -
+    SR3, SD1 / SD2, src/gpu/rowsort_kernels.hip).
+
+    ``csr``: any device CSR the other ops take -- 32- or 64-bit ``index``,
+    optional float32 ``value``, optional ``field`` of index's dtype, ``offset``
+    possibly a slice of a larger row pointer, empty rows, no rows; a
+    transpose's pair views are unpaired first.  The sort key of an entry is
+    ``(index, field)`` for ``by="index"`` and ``(field, index)`` for
+    ``by="field"`` (which needs ``field``); without ``field`` it is ``index``.
+    The order is ascending and stable: entries of equal keys keep their input
+    order.
+
+    ``duplicates="keep"``: every entry survives.  Nothing is read back, so the
+    entry arrays keep the input arrays' length: the rows' entries lie at
+    ``[0, offset[-1])`` and whatever a row slice leaves behind them is zero.
+    ``"first"``: of each run of equal keys the first entry in input order
+    survives.  ``"sum"``: one entry per run, its value the float32 sum of the
+    run's values added one by one in input order; a CSR without ``value``
+    raises ``ValueError`` (a repeated implicit 1.0 would have to become 2.0:
+    use ``"first"``).  These two read one device word, the new entry count, to
+    size their outputs exactly.
+
+    Returns a new dict: ``offset`` int64 from 0, ``index`` / ``value`` /
+    ``field`` new tensors of the input's dtypes (only the columns the input
+    has), every other key (``label``, ``weight``, ``qid``, ``group_ptr``, ...)
+    the same object.  The input is not modified, and the output bytes are a
+    pure function of it (no atomics).  A row sorts in one wave's registers (up
+    to ``_dmlc.sort_wave_row_entries()`` entries), in one workgroup's LDS (up to
+    ``_dmlc.sort_block_row_entries()``) or by LDS tiles and merge passes; rows
+    longer than that merge through 4 bytes per entry of the persistent
+    workspace of :func:`transpose`.  A row whose pointers descend or leave the
+    entry arrays forms no address, is left out and sets a device error word:
+    ``"first"`` and ``"sum"`` raise ``ValueError`` after the launch, as
+    :func:`gather_rows` does.  ``"keep"`` does not synchronise, so it cannot
+    raise: the word travels as ``result["sort_error"]`` (int32 ``[1]``, 0: all
+    rows sorted), and :func:`row_order` of the result raises for such a row
+    pointer."""
+    if duplicates not in ("keep", "first", "sum"):
+        raise ValueError(f"sort_rows: duplicates must be 'keep', 'first' or 'sum', "
+                         f"got {duplicates!r}")
+    if duplicates == "sum" and by in ("index", "field") and csr.get("value") is None:
+        raise ValueError("sort_rows: duplicates='sum' needs csr['value'] (summing implicit 1.0s "
+                         "would change the schema); use duplicates='first'")
+    csr, view, nrows, entries = _sort_operand("sort_rows", csr, by)
+    index, dev, stream = csr["index"], csr["index"].device, _stream()
+    columns = [k for k in ("index", "value", "field") if isinstance(csr.get(k), torch.Tensor)]
+    by_field = by == "field"
+    res = dict(csr)
+    if nrows == 0:
+        res["offset"] = torch.zeros(1, dtype=torch.int64, device=dev)
+        for k in columns:
+            res[k] = torch.zeros(entries if duplicates == "keep" else 0, dtype=csr[k].dtype,
+                                 device=dev)
+        return res
+    error = torch.zeros(1, dtype=torch.int32, device=dev)
+    offset = torch.empty(nrows + 1, dtype=torch.int64, device=dev)
+    kept = {k: torch.empty(entries, dtype=csr[k].dtype, device=dev) for k in columns}
+    scratch = _workspace(4 * entries + 8 * _dmlc.csr_gather_scratch_words(nrows) + 16, dev)
+    _dmlc.sort_rows(view, entries, by_field, _ptr(offset), _ptr(kept["index"]),
+                    _ptr(kept.get("value")), _ptr(kept.get("field")), _ptr(scratch), _ptr(error),
+                    stream)
+    if duplicates == "keep":
+        res.update(kept, offset=offset, sort_error=error)  # nothing is read back
+        return res
+    # SD1 + scan over the sorted rows, one read to size the outputs, SD2
+    sorted_view = (_ptr(offset), _ptr(kept["index"]), _ptr(kept.get("value")),
+                   _ptr(kept.get("field")), nrows, view[5], False)
+    status = torch.zeros(2, dtype=torch.int64, device=dev)  # [entries kept, error word]
+    new_offset = torch.empty(nrows + 2, dtype=torch.int64, device=dev)
+    scan = (_ptr(scratch) + 4 * entries + 15) // 16 * 16
+    _dmlc.sort_rows_count(sorted_view, entries, by_field, _ptr(new_offset), scan, _ptr(status),
+                          _ptr(status) + 8, stream)
+    nnz, err = status.tolist()
+    _raise_sort_errors("sort_rows", err | int(error.item()))
+    out = {k: torch.empty(nnz, dtype=csr[k].dtype, device=dev) for k in columns}
+    _dmlc.sort_rows_heads(sorted_view, entries, by_field, duplicates == "sum", _ptr(new_offset),
+                          _ptr(status), _ptr(out["index"]), _ptr(out.get("value")),
+                          _ptr(out.get("field")), nnz, _ptr(status) + 8, stream)
+    res.update(out, offset=new_offset[:nrows + 1])
+    return res
+
+
+def row_order(csr: Dict, by: str = "index") -> Dict:
+    """Whether the rows of a device CSR are in :func:`sort_rows`' order, and
+    how many entries repeat a key: ``{"sorted": bool, "duplicates": int}`` (SD1
+    without a write target: one small kernel, one read).
+
+    ``sorted``: no entry's key is below its predecessor's in the same row.
+    ``duplicates``: entries whose key equals that of the entry before them in
+    the same row.  For sorted rows that is exactly the number of entries that
+    repeat an earlier key of their row (what ``duplicates="first"`` removes);
+    for unsorted rows only adjacent repeats are counted, so the number is a
+    lower bound.  The key is :func:`sort_rows`': ``by="field"`` needs
+    ``csr["field"]``."""
+    csr, view, nrows, entries = _sort_operand("row_order", csr, by)
+    if nrows == 0:
+        return {"sorted": True, "duplicates": 0}
+    status = torch.zeros(3, dtype=torch.int64, device=csr["index"].device)
+    _dmlc.row_order(view, entries, by == "field", _ptr(status), _ptr(status) + 16, _stream())
+    unsorted, repeats, err = status.tolist()
+    _raise_sort_errors("row_order", err)
+    return {"sorted": not unsorted, "duplicates": int(repeats)}
 
 
 def _source_key(csr: Dict, num_features: int):

@@ -39,6 +39,9 @@ def main():
                     help="a fresh row permutation of the resident CSR every epoch "
                          "(data.RowBatches: device row gather) instead of file order")
     ap.add_argument("--shuffle-seed", type=int, default=0)
+    ap.add_argument("--sort-rows", action="store_true",
+                    help="sort every row's entries by field once (ops.sort_rows): the order in "
+                         "which FF2's atomic adds are contiguous, for files not written that way")
     args = ap.parse_args()
 
     import torch
@@ -68,6 +71,8 @@ def main():
     _, max_field = dist.global_stats([0], csr.max_field)
     num_features, num_fields = max_index + 1, max_field + 1
     t = data.csr_to_torch(csr)
+    if args.sort_rows:
+        t = ops.sort_rows(t, by="field")
     if args.uri is None:
         g = torch.Generator(device="cpu").manual_seed(11)  # the same teacher on every rank
         lin = torch.randn(num_features, generator=g).cuda()

@@ -28,6 +28,12 @@
  *   RK2 rank, block/group the same launchers, groups above kRankWaveGroupRows
  *   G1 row gather count  LaunchCSRGatherCount     (gather_kernels.hip)
  *   G2 row gather fill   LaunchCSRGatherFill      (gather_kernels.hip)
+ *   SR0 sort row pointer LaunchSortRows           (rowsort_kernels.hip)
+ *   SR1 sort, wave/row   LaunchSortRows, rows up to kSortWaveRowEntries
+ *   SR2 sort, block/row  LaunchSortRows, rows up to kSortBlockRowEntries
+ *   SR3 sort, long rows  LaunchSortRows, LDS tiles + merge-path passes
+ *   SD1 runs per row     LaunchRowRuns            (rowsort_kernels.hip; + K3)
+ *   SD2 run heads / sums LaunchRowHeads           (rowsort_kernels.hip)
  *   CSR -> CSC           LaunchCSRTranspose       (transpose_kernels.hip)
  *   U1 compact mark      LaunchCompactMark        (compact_kernels.hip)
  *   U2 compact count     LaunchCompactCount       (compact_kernels.hip; + K3)
@@ -684,6 +690,56 @@ void LaunchCSRGatherFill(const CsrView& src, uint64_t src_entries, const void* r
                          size_t n_sel, uint64_t* out_offset, const uint64_t* total,
                          void* out_index, float* out_value, void* out_field,
                          uint64_t out_capacity, uint32_t* error, hipStream_t stream);
+// ------------- canonical rows: segmented sort (rowsort_kernels.hip) -------------
+/*! \brief entries of a row SR1 sorts in one wave's registers (4 per lane) */
+constexpr uint32_t kSortWaveRowEntries = 256;
+/*! \brief entries of a row SR2 holds whole in a workgroup's LDS; SR3's tile */
+constexpr uint32_t kSortBlockRowEntries = 4096;
+/*! \brief output entries of one merge-path segment of SR3's merge passes */
+constexpr uint32_t kSortMergeTile = 16;
+/*! \brief bits of the row sort's device error word */
+constexpr uint32_t kSortErrOffset = 1;     // a row pointer descends or leaves the entry arrays
+constexpr uint32_t kSortErrCapacity = 2;   // more run heads than out_capacity
+constexpr uint32_t kSortErrRowLength = 4;  // a row of 2^32 entries or more
+/*!
+ * \brief SR0 - SR3: every row of src with its entries sorted ascending by
+ *  (index, field) -- by_field: (field, index), which needs src.field; without a
+ *  field column by index alone -- and stable: entries of equal keys keep their
+ *  input order.  src: the CSR shapes of K11 (value may be null, offset may be a
+ *  slice, 32- or 64-bit ids, no pairs).  src_entries: entries of src's index /
+ *  value / field and of out_index / out_value / out_field (src's types; a
+ *  column src lacks may be null).  out_offset [nrows + 1] = offset - offset[0];
+ *  row r's entries go to out_*[out_offset[r] ..), and the entries past the
+ *  last row are zeroed.  scratch: src_entries u32 words (rows longer than
+ *  kSortBlockRowEntries merge through it).  Four launches over all rows; no row
+ *  length is needed on the host.  A row whose pointers descend, start before
+ *  offset[0] or end past src_entries is left out and ORs kSortErrOffset into
+ *  *error (a device word the caller zeroed).  No atomics on the outputs;
+ *  nrows == 0 returns before any HIP call.
+ */
+void LaunchSortRows(const CsrView& src, uint64_t src_entries, bool by_field, uint64_t* out_offset,
+                    void* out_index, float* out_value, void* out_field, uint32_t* scratch,
+                    uint32_t* error, hipStream_t stream);
+/*!
+ * \brief SD1: counts[r] (may be null) = runs of equal keys in row r, the
+ *  distinct keys of a sorted row.  status (may be null; two u64 the caller
+ *  zeroed): word 0 becomes 1 if any entry's key is below its predecessor's,
+ *  word 1 receives the entries whose key equals their predecessor's.  A row
+ *  that cannot be used counts 0 and ORs kSortErrOffset into *error.
+ */
+void LaunchRowRuns(const CsrView& sorted, uint64_t src_entries, bool by_field, uint64_t* counts,
+                   uint64_t* status, uint32_t* error, hipStream_t stream);
+/*!
+ * \brief SD2: the head of every run of row r to out_*[out_offset[r] + rank]
+ *  (out_offset: SD1's counts scanned by LaunchScanU64; the closing slot
+ *  out_offset[nrows] is written here from *total).  The head is the run's
+ *  first entry in input order; with `sum` its value is the f32 sum of the
+ *  run's values added one by one in that order.  A position at or past
+ *  out_capacity is not written (kSortErrCapacity when the total exceeds it).
+ */
+void LaunchRowHeads(const CsrView& sorted, uint64_t src_entries, bool by_field, bool sum,
+                    uint64_t* out_offset, const uint64_t* total, void* out_index, float* out_value,
+                    void* out_field, uint64_t out_capacity, uint32_t* error, hipStream_t stream);
 // ------------- compact feature ids of a batch (compact_kernels.hip) -------------
 /*! \brief largest num_features of U1 - U4 (the bitmap's bits) */
 constexpr uint64_t kCompactMaxFeatures = 1ull << 32;

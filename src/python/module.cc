@@ -1179,6 +1179,64 @@ PYBIND11_MODULE(_dmlc, m) {
       py::arg("n_sel"), py::arg("out_offset"), py::arg("total"), py::arg("out_index"),
       py::arg("out_value"), py::arg("out_field"), py::arg("out_capacity"), py::arg("error"),
       py::arg("stream"));
+  m.def(
+      "sort_rows",
+      [stream_of](const CsrArg& csr, uint64_t src_entries, bool by_field, uintptr_t out_offset,
+                  uintptr_t out_index, uintptr_t out_value, uintptr_t out_field, uintptr_t scratch,
+                  uintptr_t error, uintptr_t stream) {
+        gpu::LaunchSortRows(View(csr), src_entries, by_field, Ptr<uint64_t>(out_offset),
+                            Ptr<void>(out_index), Ptr<float>(out_value), Ptr<void>(out_field),
+                            Ptr<uint32_t>(scratch), Ptr<uint32_t>(error), stream_of(stream));
+      },
+      py::arg("csr"), py::arg("src_entries"), py::arg("by_field"), py::arg("out_offset"),
+      py::arg("out_index"), py::arg("out_value"), py::arg("out_field"), py::arg("scratch"),
+      py::arg("error"), py::arg("stream"));
+  m.def(
+      "row_order",
+      [stream_of](const CsrArg& csr, uint64_t src_entries, bool by_field, uintptr_t status,
+                  uintptr_t error, uintptr_t stream) {
+        gpu::LaunchRowRuns(View(csr), src_entries, by_field, nullptr, Ptr<uint64_t>(status),
+                           Ptr<uint32_t>(error), stream_of(stream));
+      },
+      py::arg("csr"), py::arg("src_entries"), py::arg("by_field"), py::arg("status"),
+      py::arg("error"), py::arg("stream"));
+  m.def(
+      "sort_rows_count",
+      [stream_of](const CsrArg& csr, uint64_t src_entries, bool by_field, uintptr_t out_offset,
+                  uintptr_t scratch, uintptr_t total, uintptr_t error, uintptr_t stream) {
+        // SD1 and the scan of its counts: out_offset[0 .. nrows) becomes the
+        // new row pointer, *total its entry count
+        const gpu::CsrView view = View(csr);
+        auto* oo = Ptr<uint64_t>(out_offset);
+        gpu::LaunchRowRuns(view, src_entries, by_field, oo, nullptr, Ptr<uint32_t>(error),
+                           stream_of(stream));
+        if (view.nrows != 0) {
+          gpu::LaunchScanU64(oo, view.nrows, Ptr<uint64_t>(scratch), Ptr<uint64_t>(total),
+                             stream_of(stream));
+        }
+      },
+      py::arg("csr"), py::arg("src_entries"), py::arg("by_field"), py::arg("out_offset"),
+      py::arg("scratch"), py::arg("total"), py::arg("error"), py::arg("stream"));
+  m.def(
+      "sort_rows_heads",
+      [stream_of](const CsrArg& csr, uint64_t src_entries, bool by_field, bool sum,
+                  uintptr_t out_offset, uintptr_t total, uintptr_t out_index, uintptr_t out_value,
+                  uintptr_t out_field, uint64_t out_capacity, uintptr_t error, uintptr_t stream) {
+        gpu::LaunchRowHeads(View(csr), src_entries, by_field, sum, Ptr<uint64_t>(out_offset),
+                            Ptr<const uint64_t>(total), Ptr<void>(out_index), Ptr<float>(out_value),
+                            Ptr<void>(out_field), out_capacity, Ptr<uint32_t>(error),
+                            stream_of(stream));
+      },
+      py::arg("csr"), py::arg("src_entries"), py::arg("by_field"), py::arg("sum"),
+      py::arg("out_offset"), py::arg("total"), py::arg("out_index"), py::arg("out_value"),
+      py::arg("out_field"), py::arg("out_capacity"), py::arg("error"), py::arg("stream"));
+  m.def("sort_wave_row_entries", []() { return gpu::kSortWaveRowEntries; },
+        "entries of a row SR1 (one wave per row) sorts in registers; longer rows run on SR2");
+  m.def("sort_block_row_entries", []() { return gpu::kSortBlockRowEntries; },
+        "entries of a row SR2 holds whole in LDS; longer rows are tiled and merged by SR3");
+  m.attr("sort_err_offset") = gpu::kSortErrOffset;
+  m.attr("sort_err_capacity") = gpu::kSortErrCapacity;
+  m.attr("sort_err_row_length") = gpu::kSortErrRowLength;
   m.def("csr_gather_scratch_words", &gpu::CSRGatherScratchWords, py::arg("n_sel"));
   m.def("csr_gather_run_entries", &gpu::CSRGatherRunEntries);
   m.def(
