@@ -436,17 +436,42 @@ class SparseGBDT:
     behave as they do for XGBoost).  Labels are relevance grades in [0, 31],
     margins are scores; a row without a pair has g = h = 0 and only follows the
     splits.  Row weights are refused, not ignored.  :meth:`fit` takes the
-    groups from ``csr["group_ptr"]`` or the runs of ``csr["qid"]``."""
+    groups from ``csr["group_ptr"]`` or the runs of ``csr["qid"]``.
+
+    Vector leaves (``num_outputs = K > 1``, XGBoost's
+    ``multi_strategy="multi_output_tree"``): one tree per round whose leaves
+    hold K values.  All outputs share the rows' nodes, so the cuts, the bins
+    and :func:`~dmlc_core_amd.ops.advance_rows` are the scalar model's; the
+    levels run :func:`~dmlc_core_amd.ops.grad_histogram_multi` ->
+    :func:`~dmlc_core_amd.ops.best_splits_multi`.  Margins are ``[rows, K]``
+    and ``leaf`` is float32 ``[size, K]``, ``-lr G_k / (H_k + lambda)``;
+    ``min_child_weight`` bounds a child's mean hessian per output.
+    ``"softmax"`` (K >= 2): labels are class ids in [0, K), ``g = p - onehot``,
+    ``h = max(2 p (1 - p), 1e-16)``, the loss is the mean cross entropy.
+    ``"squared"`` / ``"logistic"``: labels are ``[rows, K]`` (multi-target,
+    multi-label) and the scalar formulas apply per output; row weights
+    multiply every output.  Rank objectives have one output.  Out of scope: a
+    fused forest walk that sums vector margins (``method="rows"`` gathers the
+    vector leaves of GB6's leaf ids in torch), and one-tree-per-class boosting."""
 
     _RANK_WEIGHTING = {"rank:ndcg": "ndcg", "rank:pairwise": "none"}
 
     def __init__(self, num_features: int, max_bins: int = 256, max_depth: int = 6,
                  learning_rate: float = 0.3, reg_lambda: float = 1.0, gamma: float = 0.0,
                  min_child_weight: float = 1.0, objective: str = "logistic",
-                 rank_sigma: float = 1.0, rank_normalize: str = "none"):
-        if objective not in ("logistic", "squared") + tuple(self._RANK_WEIGHTING):
-            raise ValueError("objective must be 'logistic', 'squared', 'rank:ndcg' or "
+                 rank_sigma: float = 1.0, rank_normalize: str = "none", num_outputs: int = 1):
+        if objective not in ("logistic", "squared", "softmax") + tuple(self._RANK_WEIGHTING):
+            raise ValueError("objective must be 'logistic', 'squared', 'softmax', 'rank:ndcg' or "
                              f"'rank:pairwise', got {objective!r}")
+        kmax = int(_dmlc().gbdt_max_outputs())
+        if isinstance(num_outputs, bool) or not isinstance(num_outputs, int) \
+                or not 1 <= num_outputs <= kmax:
+            raise ValueError(f"num_outputs must be an int in [1, {kmax}], got {num_outputs!r}")
+        if objective == "softmax" and num_outputs < 2:
+            raise ValueError("objective 'softmax' needs num_outputs >= 2, one per class")
+        if objective in self._RANK_WEIGHTING and num_outputs > 1:
+            raise ValueError(f"objective {objective!r} has one output, got num_outputs="
+                             f"{num_outputs}")
         if isinstance(rank_sigma, bool) or not isinstance(rank_sigma, (int, float)) \
                 or not rank_sigma > 0:
             raise ValueError(f"rank_sigma must be a number > 0, got {rank_sigma!r}")
@@ -461,6 +486,7 @@ class SparseGBDT:
         self.reg_lambda, self.gamma = float(reg_lambda), float(gamma)
         self.min_child_weight, self.objective = float(min_child_weight), objective
         self.rank_sigma, self.rank_normalize = float(rank_sigma), rank_normalize
+        self.num_outputs = num_outputs
         self.cuts = None    # feature_cuts of the training data
         self.trees = []     # dicts of feature / bin / default_left / leaf
         self.margin = None  # the training rows' margins, updated by boost()
@@ -489,7 +515,13 @@ class SparseGBDT:
         if weighting is not None:  # boost() has checked weight and group_ptr
             return ops.rank_grad_hess(margin, label, group_ptr, weighting, self.rank_sigma,
                                       self.rank_normalize)
-        if self.objective == "logistic":
+        if self.num_outputs > 1 and weight is not None:
+            weight = weight.reshape(-1, 1)  # a row's weight multiplies every output
+        if self.objective == "softmax":
+            p = torch.softmax(margin, 1)
+            g = p - torch.nn.functional.one_hot(label.long(), self.num_outputs)
+            h = (2.0 * p * (1.0 - p)).clamp_min(1e-16)
+        elif self.objective == "logistic":
             p = torch.sigmoid(margin)
             g, h = p - label, p * (1.0 - p)
         else:
@@ -505,6 +537,11 @@ class SparseGBDT:
         weighting = self._rank_groups("loss", weight, group_ptr)
         if weighting is not None:
             return rank_loss(margin, label, group_ptr, weighting, self.rank_sigma)
+        if self.objective == "softmax":
+            ce = torch.nn.functional.cross_entropy(margin, label.long(), reduction="none")
+            return (ce * weight).mean() if weight is not None else ce.mean()
+        if self.num_outputs > 1 and weight is not None:
+            weight = weight.reshape(-1, 1)
         return _fm_loss(margin, label, weight, self.objective)
 
     @torch.no_grad()
@@ -525,6 +562,7 @@ class SparseGBDT:
         self._device_csr(csr)
         group_ptr = _group_ptr(csr) if self.objective in self._RANK_WEIGHTING else None
         self._rank_groups("fit", csr.get("weight"), group_ptr)
+        self._check_labels(csr["label"], int(csr["offset"].numel()) - 1)
         if check_rows:
             # by id alone: a field column is no part of a GBDT feature
             order = ops.row_order({k: v for k, v in csr.items() if k != "field"})
@@ -550,38 +588,43 @@ class SparseGBDT:
         rows, dev = int(binned["rows"]), binned["row"].device
         if self.cuts is None:
             self.cuts = {"cut_ptr": binned["cut_ptr"], "cut": binned["cut"]}
+        K = self.num_outputs
+        many = (K,) if K > 1 else ()  # the trailing axis of margins, leaves and sums
         if self.margin is None:
-            self.margin = torch.zeros(rows, dtype=torch.float32, device=dev)
-        elif self.margin.numel() != rows:
+            self.margin = torch.zeros((rows,) + many, dtype=torch.float32, device=dev)
+        elif self.margin.shape[0] != rows:
             raise ValueError(f"SparseGBDT.boost: the model tracks the margins of "
-                             f"{self.margin.numel()} training rows, binned has {rows}: the trees "
+                             f"{self.margin.shape[0]} training rows, binned has {rows}: the trees "
                              "were grown on another matrix (fit() starts a new model)")
         label = label.to(device=dev, dtype=torch.float32)
+        self._check_labels(label, rows)
         g, h = self._gradients(self.margin, label, weight, group_ptr)
         scale = ops.gradient_scale(g, h)
         qgh = torch.stack([torch.round(g.double() * scale), torch.round(h.double() * scale)],
-                          1).long()
+                          -1).long()
         size = 2 ** (self.max_depth + 1) - 1
         tree = {"feature": torch.full((size,), -1, dtype=torch.int64, device=dev),
                 "bin": torch.zeros(size, dtype=torch.int32, device=dev),
                 "default_left": torch.zeros(size, dtype=torch.bool, device=dev),
-                "leaf": torch.zeros(size, dtype=torch.float32, device=dev)}
+                "leaf": torch.zeros((size,) + many, dtype=torch.float32, device=dev)}
+        histogram, splits = ((ops.grad_histogram_multi, ops.best_splits_multi) if K > 1 else
+                             (ops.grad_histogram, ops.best_splits))
         pos = torch.zeros(rows, dtype=torch.int32, device=dev)
         for depth in range(self.max_depth + 1):
             first, n = 2 ** depth - 1, 2 ** depth
             ids = torch.arange(first, first + n, dtype=torch.int32, device=dev)
             node = pos.long() - first
             live = (node >= 0) & (node < n)
-            node_sum = torch.zeros((n, 2), dtype=torch.int64, device=dev)
+            node_sum = torch.zeros((n,) + many + (2,), dtype=torch.int64, device=dev)
             node_sum.index_add_(0, node[live], qgh[live])
             sums = node_sum.double() / scale
             tree["leaf"][first:first + n] = \
-                (-self.learning_rate * sums[:, 0] / (sums[:, 1] + self.reg_lambda)).float()
+                (-self.learning_rate * sums[..., 0] / (sums[..., 1] + self.reg_lambda)).float()
             if depth == self.max_depth:
                 break
-            hist = ops.grad_histogram(binned, g, h, pos, n, scale, first_node=first)
-            split = ops.best_splits(hist, node_sum, binned["cut_ptr"], scale, self.reg_lambda,
-                                    self.gamma, self.min_child_weight)
+            hist = histogram(binned, g, h, pos, n, scale, first_node=first)
+            split = splits(hist, node_sum, binned["cut_ptr"], scale, self.reg_lambda,
+                           self.gamma, self.min_child_weight)
             for k in ("feature", "bin", "default_left"):
                 tree[k][first:first + n] = split[k]
             pos = ops.advance_rows(binned, pos, split, *self._children(split, ids), first_node=first)
@@ -589,6 +632,25 @@ class SparseGBDT:
         self._packed = None
         self.margin = self.margin + tree["leaf"][pos.long()]
         return self.margin
+
+    def _check_labels(self, label, rows: int) -> None:
+        """the labels' shape for K > 1 and, under ``"softmax"``, their range: one read"""
+        K = self.num_outputs
+        if self.objective == "softmax":
+            if tuple(label.shape) != (rows,):
+                raise ValueError(f"SparseGBDT: 'softmax' takes {rows} class ids, got labels of "
+                                 f"shape {tuple(label.shape)}")
+            if rows == 0:
+                return
+            lab = label.double()
+            lo, hi, whole = torch.stack([lab.min(), lab.max(),
+                                         (lab == lab.round()).all().double()]).tolist()
+            if not whole or not (0 <= lo and hi < K):  # a NaN fails `whole`
+                raise ValueError(f"labels must be integers in [0, {K}); got min {lo}, max {hi}"
+                                 + ("" if whole else ", not all integers"))
+        elif K > 1 and tuple(label.shape) != (rows, K):
+            raise ValueError(f"SparseGBDT: num_outputs={K} takes labels [{rows}, {K}], got "
+                             f"{tuple(label.shape)}")
 
     @staticmethod
     def _children(split, ids):
@@ -601,11 +663,24 @@ class SparseGBDT:
         """the trees packed for GB6, repacked when their number has changed (and only then: a
         tree replaced in place, or new ``cuts``, needs ``self._packed = None``)"""
         if self._packed is None or self._packed["trees"] != len(self.trees):
-            self._packed = ops.pack_forest(self.trees, self.cuts)
+            trees = self.trees
+            if self.num_outputs > 1:  # GB6 walks to leaf ids only: a zero stands in for the vector
+                trees = [dict(t, leaf=torch.zeros_like(t["leaf"][:, 0])) for t in trees]
+            self._packed = ops.pack_forest(trees, self.cuts)
         return self._packed
 
+    def _gather_leaves(self, ids) -> torch.Tensor:
+        """the margins ``[rows, K]`` of vector-leaf trees from the nodes ``ids [rows, T]`` the
+        rows end on, summed in f32 in tree order (the order of the level-by-level path)"""
+        margin = torch.zeros((ids.shape[0], self.num_outputs), dtype=torch.float32,
+                             device=ids.device)
+        for t, tree in enumerate(self.trees):
+            margin = margin + tree["leaf"][ids[:, t].long()]
+        return margin
+
     def predict(self, csr, method: str = "levels") -> torch.Tensor:
-        """The margins of the rows of ``csr`` (logits under ``"logistic"``).
+        """The margins of the rows of ``csr`` (logits under ``"logistic"`` and
+        ``"softmax"``; ``[rows, num_outputs]`` with vector leaves).
         ``method="levels"``: binned with the stored cuts (a transpose of
         ``csr``), walked down every tree level by level, one
         :func:`~dmlc_core_amd.ops.advance_rows` per tree and level.
@@ -619,10 +694,13 @@ class SparseGBDT:
         if self.cuts is None:
             raise ValueError("SparseGBDT.predict: the model has no cuts (fit or boost first)")
         if method == "rows":
+            if self.num_outputs > 1:
+                return self._gather_leaves(ops.predict_forest(csr, self._forest(), "leaf"))
             return ops.predict_forest(csr, self._forest(), "margin")
         binned = ops.bin_features(csr, self.cuts, self.num_features)
         rows, dev = int(binned["rows"]), binned["row"].device
-        margin = torch.zeros(rows, dtype=torch.float32, device=dev)
+        many = (self.num_outputs,) if self.num_outputs > 1 else ()
+        margin = torch.zeros((rows,) + many, dtype=torch.float32, device=dev)
         for tree in self.trees:
             margin = margin + tree["leaf"][self._walk_levels(binned, tree).long()]
         return margin

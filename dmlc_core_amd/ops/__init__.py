@@ -8,6 +8,8 @@ rowsort_kernels.hip).
 Histogram gradient-boosted trees run on the column-major binned matrix:
 :func:`feature_cuts` -> :func:`bin_features` once, then per tree level
 :func:`grad_histogram` -> :func:`best_splits` -> :func:`advance_rows`.
+Trees with K values per leaf (multiclass, multi-target) take the K-channel
+:func:`grad_histogram_multi` -> :func:`best_splits_multi` instead.
 The trained forest scores row-major batches in one launch:
 :func:`pack_forest` once, then :func:`predict_forest` for margins or leaf ids.
 Ranking on query groups: :func:`qid_groups`, then :func:`rank_loss` / :func:`ndcg`
@@ -38,6 +40,7 @@ __all__ = ["spmv", "spmv_t", "hashed_dense", "SpMVFunction", "csr_spmv", "transp
            "qid_groups", "group_rows", "rank_loss", "rank_loss_parts", "rank_grad_hess",
            "RankLossFunction", "ndcg",
            "feature_cuts", "bin_features", "gradient_scale", "grad_histogram", "best_splits",
+           "grad_histogram_multi", "best_splits_multi",
            "advance_rows", "pack_forest", "predict_forest"]
 
 # persistent transpose scratch per (device, stream), grow-only: a rebuild (a
@@ -1642,6 +1645,100 @@ def best_splits(hist: torch.Tensor, node_sum: torch.Tensor, cut_ptr: torch.Tenso
                                float(min_child_weight), (_ptr(ws) + 15) // 16 * 16,
                                _ptr(res["feature"]), _ptr(res["bin"]), _ptr(res["default_left"]),
                                _ptr(res["gain"]), _stream())
+    return res
+
+
+def _check_outputs(name: str, what: str, t, rows: int, dev, outputs=None) -> int:
+    """``t`` as float32 ``[rows, K]`` gradients; returns K"""
+    kmax = int(_dmlc.gbdt_max_outputs())
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 \
+            or t.shape[0] != rows or t.device != dev or not t.is_contiguous():
+        raise ValueError(f"{name}: {what} must be a contiguous float32 tensor [{rows}, K] on {dev}")
+    k = int(t.shape[1])
+    if not 1 <= k <= kmax or (outputs is not None and k != outputs):
+        raise ValueError(f"{name}: {what} has {k} outputs, expected "
+                         + (f"{outputs}" if outputs is not None else f"1 to {kmax}"))
+    return k
+
+
+def grad_histogram_multi(binned: Dict, grad: torch.Tensor, hess: torch.Tensor, pos: torch.Tensor,
+                         num_nodes: int, scale: float, first_node: int = 0) -> torch.Tensor:
+    """:func:`grad_histogram` for K gradients per row (GB3m, vector-leaf
+    trees), int64 ``[num_nodes, total_bins, K, 2]``: cell ``[n, cut_ptr[f] +
+    bin, k, :]`` sums ``(llrint(g[r, k] * scale), llrint(h[r, k] * scale))``
+    over the entries of the rows in node n.
+
+    ``grad`` / ``hess``: contiguous float32 ``[rows, K]``, ``1 <= K <=
+    _dmlc.gbdt_max_outputs()``; ``pos``, the window and ``scale`` as for
+    :func:`grad_histogram` (:func:`gradient_scale` of the 2-D tensors).  The
+    binned matrix and ``pos`` are read once for all K outputs: a group of
+    lanes owns an entry, one lane per output, and reads the row's K gradients
+    as one contiguous piece.  The LDS table tiles the nodes, and for a column
+    too wide for all K outputs of one node the outputs.  Integer sums: the
+    same bytes on every run.  Nothing is read back."""
+    name = "grad_histogram_multi"
+    arg = _binned_arg(name, binned)
+    _check_window(name, num_nodes, first_node)
+    rows, total, dev = arg[6], arg[7], binned["row"].device
+    k = _check_outputs(name, "grad", grad, rows, dev)
+    _check_outputs(name, "hess", hess, rows, dev, k)
+    _check_rows(name, "pos", pos, torch.int32, rows, dev)
+    if not float(scale) > 0:
+        raise ValueError(f"{name}: scale must be > 0, got {scale!r}")
+    hist = torch.zeros((num_nodes, total, k, 2), dtype=torch.int64, device=dev)
+    if rows > 0 and total > 0 and arg[5] > 0:
+        _dmlc.gbdt_histogram_multi(arg, _ptr(grad), _ptr(hess), _ptr(pos), first_node, num_nodes, k,
+                                   float(scale), _ptr(hist), _stream())
+    return hist
+
+
+def best_splits_multi(hist: torch.Tensor, node_sum: torch.Tensor, cut_ptr: torch.Tensor,
+                      scale: float, reg_lambda: float = 1.0, gamma: float = 0.0,
+                      min_child_weight: float = 1.0) -> Dict:
+    """:func:`best_splits` for K outputs (GB4m): the same dict, candidates and
+    tie order, from ``hist`` int64 ``[N, total_bins, K, 2]``
+    (:func:`grad_histogram_multi`) and ``node_sum`` int64 ``[N, K, 2]``.
+
+    ``gain = 0.5 * sum_k (GL_k^2/(HL_k+l) + GR_k^2/(HR_k+l) - G_k^2/(H_k+l))
+    - gamma`` on the float64 sums divided by ``scale``.  A candidate is valid
+    with ``sum_k HL_k >= K * min_child_weight * scale`` and the same on the
+    right, on the integer sums: ``min_child_weight`` bounds the mean hessian
+    per output.  A group of lanes owns a (node, feature), one lane per
+    output, and the sum over k is a shuffle butterfly in a fixed order: two
+    calls give the same bytes."""
+    name = "best_splits_multi"
+    kmax = int(_dmlc.gbdt_max_outputs())
+    if not isinstance(hist, torch.Tensor) or hist.dtype != torch.int64 or hist.dim() != 4 \
+            or hist.shape[3] != 2 or not 1 <= hist.shape[2] <= kmax or not hist.is_cuda \
+            or not hist.is_contiguous():
+        raise ValueError(f"{name}: hist must be a contiguous int64 device tensor [N, bins, K, 2], "
+                         f"K in [1, {kmax}]")
+    n, total, k, dev = int(hist.shape[0]), int(hist.shape[1]), int(hist.shape[2]), hist.device
+    if not isinstance(node_sum, torch.Tensor) or node_sum.dtype != torch.int64 \
+            or tuple(node_sum.shape) != (n, k, 2) or node_sum.device != dev \
+            or not node_sum.is_contiguous():
+        raise ValueError(f"{name}: node_sum must be a contiguous int64 tensor [{n}, {k}, 2] on {dev}")
+    if not isinstance(cut_ptr, torch.Tensor) or cut_ptr.dtype != torch.int64 or cut_ptr.dim() != 1 \
+            or cut_ptr.numel() < 2 or cut_ptr.device != dev or not cut_ptr.is_contiguous():
+        raise ValueError(f"{name}: cut_ptr must be a contiguous int64 tensor [F + 1] on {dev}")
+    if not float(reg_lambda) > 0:
+        raise ValueError(f"{name}: reg_lambda must be > 0, got {reg_lambda!r}")
+    if not float(scale) > 0:
+        raise ValueError(f"{name}: scale must be > 0, got {scale!r}")
+    if n > int(_dmlc.gbdt_max_nodes()):
+        raise ValueError(f"{name}: at most {int(_dmlc.gbdt_max_nodes())} nodes, got {n}")
+    nfeat = cut_ptr.numel() - 1
+    res = {"feature": torch.full((n,), -1, dtype=torch.int64, device=dev),
+           "bin": torch.zeros(n, dtype=torch.int32, device=dev),
+           "default_left": torch.zeros(n, dtype=torch.bool, device=dev),
+           "gain": torch.zeros(n, dtype=torch.float64, device=dev)}
+    if n > 0:
+        ws = _workspace(int(_dmlc.gbdt_split_scratch_bytes(n, nfeat)) + 16, dev)
+        _dmlc.gbdt_best_splits_multi(_ptr(hist), _ptr(node_sum), _ptr(cut_ptr), nfeat, total, n, k,
+                                     float(scale), float(reg_lambda), float(gamma),
+                                     float(min_child_weight), (_ptr(ws) + 15) // 16 * 16,
+                                     _ptr(res["feature"]), _ptr(res["bin"]),
+                                     _ptr(res["default_left"]), _ptr(res["gain"]), _stream())
     return res
 
 

@@ -31,11 +31,19 @@ cuts for each of 1 M features 64 nodes would need 262 GB.
              equal bit for bit.  `rows_share`: the time one pass over the CSR's
              bytes takes at the measured device copy rate, over the measured time
 
-Every figure is the median (and the fastest) of --iters host-clock windows
+  --outputs K  instead of the sections after `one-time`: ops.grad_histogram_multi
+             and ops.best_splits_multi (GB3m / GB4m, K gradients per row) at each
+             of --nodes, against K calls of the scalar op on the K columns made
+             contiguous beforehand (for the splits: on the K planes of the
+             histogram), which is how the same sums were had without them.  The
+             histograms are compared exactly
+
+Every figure is the median (and the fastest, the slowest) of --iters host-clock windows
 around one call each, ending in a device synchronise, after one warm-up call.
 Prints one JSON object; a line per section goes to stderr.
 
 usage: python scripts/bench_gbdt.py [--shard parsed|device] [--shard-rows N] [--max-bins B]
+                                    [--outputs K]
 """
 import argparse
 import json
@@ -57,6 +65,8 @@ def main():
     ap.add_argument("--nodes", default="1,8,64")
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--skip-torch", action="store_true")
+    ap.add_argument("--outputs", type=int, default=0,
+                    help="K > 0: only the one-time section and the K-output ops")
     args = ap.parse_args()
     import torch
 
@@ -77,7 +87,8 @@ def main():
             torch.cuda.synchronize()
             ms.append((time.perf_counter() - t0) * 1e3)
         ms.sort()
-        return {"ms": round(ms[len(ms) // 2], 3), "ms_min": round(ms[0], 3)}
+        return {"ms": round(ms[len(ms) // 2], 3), "ms_min": round(ms[0], 3),
+                "ms_max": round(ms[-1], 3)}
 
     def note(name, r):
         res[name] = r
@@ -147,6 +158,68 @@ def main():
     del csr["transpose"]
     ops.release_workspace()
     torch.cuda.empty_cache()
+
+    # ------------------------------------------------- K outputs (--outputs only)
+    if args.outputs > 0:
+        K = args.outputs
+        res["outputs"] = K
+        gk = torch.randn((rows, K), device=dev, generator=gen)
+        hk = torch.rand((rows, K), device=dev, generator=gen)
+        scale = ops.gradient_scale(gk, hk)
+        qgh = torch.stack([torch.round(gk.double() * scale), torch.round(hk.double() * scale)],
+                          2).long()
+        cols = [(gk[:, k].contiguous(), hk[:, k].contiguous()) for k in range(K)]  # not timed
+        cut_ptr = binned["cut_ptr"]
+
+        def timed_pair(a, b):
+            """`timed` for two ways to the same result, their windows alternating"""
+            a(), b()
+            torch.cuda.synchronize()
+            ms = ([], [])
+            for _ in range(args.iters):
+                for fn, out in zip((a, b), ms):
+                    t0 = time.perf_counter()
+                    fn()
+                    torch.cuda.synchronize()
+                    out.append((time.perf_counter() - t0) * 1e3)
+            return [{"ms": round(sorted(m)[len(m) // 2], 3), "ms_min": round(min(m), 3),
+                     "ms_max": round(max(m), 3)} for m in ms]
+
+        for n in (int(s) for s in args.nodes.split(",")):
+            pos = torch.randint(0, n, (rows,), device=dev, generator=gen, dtype=torch.int32)
+
+            def scalar_histograms():
+                for g1, h1 in cols:
+                    ops.grad_histogram(binned, g1, h1, pos, n, scale)
+            r, r1 = timed_pair(lambda: ops.grad_histogram_multi(binned, gk, hk, pos, n, scale),
+                               scalar_histograms)
+            r["hist_gb"] = round(n * total * K * 16 / 1e9, 2)
+            note(f"grad_histogram_multi_{n}", r)
+            note(f"grad_histogram_x{K}_{n}", r1)
+            res[f"scalar_over_multi_histogram_{n}"] = ratio(r1, r)
+            hist = ops.grad_histogram_multi(binned, gk, hk, pos, n, scale)
+            per_k = [hist[:, :, k].contiguous() for k in range(K)]
+            res[f"grad_histogram_multi_{n}_equal"] = all(
+                torch.equal(per_k[k], ops.grad_histogram(binned, *cols[k], pos, n, scale))
+                for k in range(K))
+            node_sum = torch.zeros((n, K, 2), dtype=torch.int64, device=dev)
+            node_sum.index_add_(0, pos.long(), qgh)
+            sums_k = [node_sum[:, k].contiguous() for k in range(K)]
+
+            def scalar_splits():
+                for k in range(K):
+                    ops.best_splits(per_k[k], sums_k[k], cut_ptr, scale)
+            r, r1 = timed_pair(lambda: ops.best_splits_multi(hist, node_sum, cut_ptr, scale),
+                               scalar_splits)
+            note(f"best_splits_multi_{n}", r)
+            note(f"best_splits_x{K}_{n}", r1)
+            res[f"scalar_over_multi_splits_{n}"] = ratio(r1, r)
+            split = ops.best_splits_multi(hist, node_sum, cut_ptr, scale)
+            res[f"splits_found_multi_{n}"] = int((split["feature"] >= 0).sum())
+            del hist, per_k, node_sum, sums_k
+            torch.cuda.empty_cache()
+        print(json.dumps(res), flush=True)
+        return
 
     # ---------------------------------------------------------------- histogram
     g = torch.randn(rows, device=dev, generator=gen)

@@ -19,6 +19,10 @@
  *                      best candidate under a total order.
  *  GB5 k_gbdt_advance_* one pass over pos (default side, leaves), then the
  *                      split columns' entries filtered by pos == node.
+ *  GB3m k_gbdt_hist_multi, GB4m k_gbdt_split_scan_multi: GB3 / GB4 for trees
+ *                      with K values per leaf (K gradients per row): a group of
+ *                      lanes per entry / per (node, feature), one lane per
+ *                      output; described at the kernels.
  *
  *  Segments.  The entries of the column-major matrix, in storage order, are
  *  cut every kGbdtSegmentEntries: workgroup s owns entries [s S, (s + 1) S).
@@ -490,6 +494,209 @@ __global__ __launch_bounds__(kThreads) void k_gbdt_advance_columns(
   }
 }
 
+// ---------------------------------------------------------------- GB3m
+/*!
+ * \brief GB3 with K gradients per row (vector-leaf trees).  The segment scheme is GB3's; the
+ *  lanes and the table are laid out for the [rows x K] gradients.  A group of Kp = 2^shift lanes
+ *  owns one entry: row[j], bin[j] and pos[r] are one address for the group and g[r, k0 + lane]
+ *  is one contiguous read of 4 kk bytes.  The table is [node][bin][k][g, h], so a group's
+ *  atomics fall on consecutive banks and a flush writes 16 kk contiguous bytes per (node, bin).
+ *  A pass holds nn nodes x kk outputs x the group's W bins, nn kk W <= kGbdtCells: all K outputs
+ *  and as many nodes as fit, or -- when W K alone is too much (a 256-cut column with K >= 16) --
+ *  one node and an even share kk of the outputs (kGbdtCells / 256 = 15 at least fit).  Unlike
+ *  GB3, a group of columns is no wider than the bins that fit with every node and output (or
+ *  one column), so only a single wide column tiles the nodes or the outputs.
+ */
+__global__ __launch_bounds__(kThreads) void k_gbdt_hist_multi(
+    const int64_t* __restrict__ col_ptr, const int32_t* __restrict__ row,
+    const uint8_t* __restrict__ bin, int64_t nnz, int64_t nfeat, const int64_t* __restrict__ cut_ptr,
+    int64_t total_bins, const float* __restrict__ grad, const float* __restrict__ hess,
+    const int32_t* __restrict__ pos, int64_t rows, int32_t first_node, int32_t num_nodes,
+    int32_t num_out, double scale, unsigned long long* __restrict__ hist) {
+  __shared__ unsigned long long s_acc[2 * kGbdtCells];
+  __shared__ uint32_t s_col[kColsLds];
+  __shared__ int64_t s_slot;
+  const int64_t K = num_out;
+  const int64_t base = static_cast<int64_t>(blockIdx.x) * kSeg;
+  const int64_t end = base + kSeg < nnz ? base + kSeg : nnz;
+  int64_t f_lo, f_hi;
+  segment_columns(col_ptr, nfeat, base, end, &s_slot, &f_lo, &f_hi);
+  const bool staged = stage_columns(col_ptr, f_lo, f_hi, base, s_col);
+  const int64_t head_end = col_ptr[f_lo] < base ? cut_ptr[f_lo + 1] : -1;
+  const int64_t tail_begin = col_ptr[f_hi + 1] > end ? cut_ptr[f_hi] : total_bins;
+  // the bins whose num_nodes x K cells fill the table once (group_end takes one column at least):
+  // a group's entries are streamed once per pass and a pass rejects, a whole lane group at a
+  // time, the entries of other nodes, so wider groups only add passes over more entries
+  int64_t room = kGbdtCells / (K * num_nodes);
+  if (room < 1) room = 1;
+  for (int64_t fa = f_lo; fa <= f_hi;) {
+    const int64_t fb = group_end(cut_ptr, fa, f_hi + 1, room, &s_slot);
+    const int64_t c0 = cut_ptr[fa];
+    int64_t width = cut_ptr[fb] - c0;
+    if (width > kGbdtCells) width = kGbdtCells;
+    const int64_t e0 = col_ptr[fa] > base ? col_ptr[fa] : base;
+    const int64_t e1 = col_ptr[fb] < end ? col_ptr[fb] : end;
+    if (width > 0 && c0 + width <= total_bins) {
+      int64_t kmax = kGbdtCells / width;  // >= 1
+      if (kmax > K) kmax = K;
+      const int64_t kpasses = (K + kmax - 1) / kmax;
+      const int64_t kper = (K + kpasses - 1) / kpasses;  // <= kmax: an even share of the outputs
+      int shift = 0;
+      while ((int64_t{1} << shift) < kper) ++shift;  // kper <= kGbdtMaxOutputs: shift <= 5
+      const int64_t lane = threadIdx.x & ((1 << shift) - 1);
+      const int64_t first_entry = threadIdx.x >> shift, step = kThreads >> shift;
+      int64_t per_pass = kGbdtCells / (width * kper);  // >= 1
+      if (per_pass > num_nodes) per_pass = num_nodes;
+      for (int64_t n0 = 0; n0 < num_nodes; n0 += per_pass) {
+        const int64_t nn = n0 + per_pass <= num_nodes ? per_pass : num_nodes - n0;
+        for (int64_t k0 = 0; k0 < K; k0 += kper) {
+          const int64_t kk = k0 + kper <= K ? kper : K - k0;
+          const int64_t cells = nn * width * kk;  // <= kGbdtCells
+          for (int64_t i = threadIdx.x; i < 2 * cells; i += kThreads) s_acc[i] = 0ull;
+          __syncthreads();
+          if (lane < kk) {
+            for (int64_t j = e0 + first_entry; j < e1; j += step) {
+              const int64_t f = column_of(staged, s_col, col_ptr, f_lo, fa, fb, base, j);
+              const int64_t cl = cut_ptr[f] - c0;
+              const int64_t nc = cut_ptr[f + 1] - cut_ptr[f];
+              const int64_t b = bin[j];
+              const uint64_t r = static_cast<uint32_t>(row[j]);
+              if (cl < 0 || b >= nc || cl + b >= width || r >= static_cast<uint64_t>(rows)) continue;
+              const int64_t node = static_cast<int64_t>(pos[r]) - first_node - n0;
+              if (node < 0 || node >= nn) continue;
+              const int64_t at = static_cast<int64_t>(r) * K + k0 + lane;
+              const long long qg = __double2ll_rn(static_cast<double>(grad[at]) * scale);
+              const long long qh = __double2ll_rn(static_cast<double>(hess[at]) * scale);
+              unsigned long long* const cell = s_acc + 2 * ((node * width + cl + b) * kk + lane);
+              atomicAdd(cell, static_cast<unsigned long long>(qg));
+              atomicAdd(cell + 1, static_cast<unsigned long long>(qh));
+            }
+          }
+          __syncthreads();
+          const uint32_t kk32 = static_cast<uint32_t>(kk);
+          const uint32_t width32 = static_cast<uint32_t>(width);
+          for (uint32_t i = threadIdx.x; i < static_cast<uint32_t>(cells); i += kThreads) {
+            const uint32_t k = i % kk32, nb = i / kk32;
+            const int64_t node = nb / width32, gb = c0 + nb % width32;
+            const unsigned long long g = s_acc[2 * i], h = s_acc[2 * i + 1];
+            unsigned long long* const dst =
+                hist + 2 * (((n0 + node) * total_bins + gb) * K + k0 + k);
+            if (gb >= head_end && gb < tail_begin) {
+              dst[0] = g;
+              dst[1] = h;
+            } else {
+              if (g != 0ull) atomicAdd(dst, g);
+              if (h != 0ull) atomicAdd(dst + 1, h);
+            }
+          }
+          __syncthreads();
+        }
+      }
+    }
+    fa = fb;
+  }
+}
+
+// ---------------------------------------------------------------- GB4m
+/*! \brief v summed over the aligned group of kKp lanes, in every lane: a butterfly of
+ *  xor-shuffles, widest first.  Both partners add the same pair, so the (float64) sum is one
+ *  value for the group and a pure function of the inputs. */
+template <int kKp, typename T>
+__device__ __forceinline__ T group_sum(T v) {
+#pragma unroll
+  for (int d = kKp >> 1; d >= 1; d >>= 1) v += __shfl_xor(v, d, dev::kWave);
+  return v;
+}
+
+/*!
+ * \brief GB4 with K outputs.  A group of kKp lanes (the power of two >= K) owns one (node,
+ *  feature) and lane k output k's running left sums; per bin the group reads 16 K contiguous
+ *  bytes of hist [N x bins x K x 2].  A workgroup walks the 256 features of its scalar
+ *  counterpart in kKp rounds of 256 / kKp groups, so the partials (and the scratch) are GB4's.
+ *  gain = 1/2 sum_k (GL_k^2 / (HL_k + l) + GR_k^2 / (HR_k + l) - G_k^2 / (H_k + l)) - gamma,
+ *  valid with sum_k HL_k and sum_k HR_k >= min_hess = K min_child_weight scale on the integer
+ *  sums.  The bin loop runs to the wave's longest column so that every shuffle has all of its
+ *  lanes; a group past its own column only idles.
+ */
+template <int kKp>
+__global__ __launch_bounds__(kThreads) void k_gbdt_split_scan_multi(
+    const long long* __restrict__ hist, const long long* __restrict__ node_sum,
+    const int64_t* __restrict__ cut_ptr, int64_t nfeat, int64_t total_bins, int32_t num_out,
+    double scale, double reg_lambda, double gamma, double min_hess, Cand* __restrict__ partial) {
+  constexpr int kGroups = kThreads / kKp;
+  const int lane = threadIdx.x % kKp, group = threadIdx.x / kKp;
+  const int64_t node = blockIdx.y, K = num_out;
+  const bool on = lane < K;  // lanes past K carry zeros
+  long long ng = 0, nh = 0;
+  if (on) {
+    ng = node_sum[2 * (node * K + lane)];
+    nh = node_sum[2 * (node * K + lane) + 1];
+  }
+  const double g_all = static_cast<double>(ng) / scale, h_all = static_cast<double>(nh) / scale;
+  const double parent = on ? g_all * g_all / (h_all + reg_lambda) : 0.0;
+  const long long nh_all = group_sum<kKp>(nh);
+  // GL^2 / (HL + l) + GR^2 / (HR + l) - G^2 / (H + l) of this lane's output
+  auto term = [&](long long qgl, long long qhl) -> double {
+    const double gl = static_cast<double>(qgl) / scale, hl = static_cast<double>(qhl) / scale;
+    const double gr = static_cast<double>(ng - qgl) / scale;
+    const double hr = static_cast<double>(nh - qhl) / scale;
+    return on ? gl * gl / (hl + reg_lambda) + gr * gr / (hr + reg_lambda) - parent : 0.0;
+  };
+  Cand best{0.0, kNoKey};
+  for (int round = 0; round < kKp; ++round) {
+    const int64_t f = static_cast<int64_t>(blockIdx.x) * kThreads + round * kGroups + group;
+    int64_t c0 = 0, nc = 0;
+    if (f < nfeat) {
+      c0 = cut_ptr[f];
+      nc = cut_ptr[f + 1] - c0;
+      if (c0 < 0 || c0 + nc > total_bins || nc > static_cast<int64_t>(kGbdtMaxBins)) nc = 0;
+    }
+    int nc_wave = static_cast<int>(nc);
+#pragma unroll
+    for (int d = dev::kWave >> 1; d >= 1; d >>= 1) {
+      const int o = __shfl_xor(nc_wave, d, dev::kWave);
+      nc_wave = o > nc_wave ? o : nc_wave;
+    }
+    // read only by a lane with an output, below its column's nc
+    const long long* const h = hist + 2 * ((node * total_bins + c0) * K + lane);
+    long long tg = 0, th = 0;
+    if (on) {
+      for (int64_t t = 0; t < nc; ++t) {
+        tg += h[2 * t * K];
+        th += h[2 * t * K + 1];
+      }
+    }
+    const long long miss_g = ng - tg, miss_h = nh - th;  // rows without an entry in f
+    const long long miss_h_all = group_sum<kKp>(miss_h);
+    long long lg = 0, lh = 0;
+    for (int t = 0; t < nc_wave; ++t) {
+      const bool live = t < nc;
+      if (live && on) {
+        lg += h[2 * t * K];
+        lh += h[2 * t * K + 1];
+      }
+      const double sum_right = group_sum<kKp>(term(lg, lh));  // missing goes right
+      const double sum_left = group_sum<kKp>(term(lg + miss_g, lh + miss_h));
+      const long long hl_right = group_sum<kKp>(lh);
+      if (!live || lane != 0) continue;
+      for (int dir = 0; dir < 2; ++dir) {
+        const long long hl = hl_right + (dir != 0 ? miss_h_all : 0ll);
+        if (!(static_cast<double>(hl) >= min_hess && static_cast<double>(nh_all - hl) >= min_hess))
+          continue;
+        const double gain = 0.5 * (dir != 0 ? sum_left : sum_right) - gamma;
+        if (gain > 0.0) {
+          const unsigned long long key = (static_cast<unsigned long long>(f) << 9) |
+                                         (static_cast<unsigned long long>(t) << 1) |
+                                         static_cast<unsigned long long>(dir);
+          best = better(best, Cand{gain, key});
+        }
+      }
+    }
+  }
+  best = block_best(best);
+  if (threadIdx.x == 0) partial[node * gridDim.x + blockIdx.x] = best;
+}
+
 int SegmentsOf(uint64_t nnz) { return static_cast<int>((nnz + kSeg - 1) / kSeg); }
 
 void CheckBinned(const char* op, uint64_t nnz, uint64_t num_features) {
@@ -572,6 +779,71 @@ void LaunchGbdtBestSplits(const int64_t* hist, const int64_t* node_sum, const in
                      reinterpret_cast<const long long*>(node_sum), cut_ptr,
                      static_cast<int64_t>(num_features), static_cast<int64_t>(total_bins), scale,
                      reg_lambda, gamma, min_child_weight, static_cast<Cand*>(scratch));
+  DMLC_HIP_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_gbdt_split_pick, dim3(num_nodes), dim3(kThreads), 0, stream,
+                     static_cast<const Cand*>(scratch), static_cast<int64_t>(parts), feature, bin,
+                     default_left, gain);
+  DMLC_HIP_CHECK_LAUNCH();
+}
+
+void LaunchGbdtHistogramMulti(const GbdtBinned& m, const float* grad, const float* hess,
+                              const int32_t* pos, int32_t first_node, uint32_t num_nodes,
+                              uint32_t num_outputs, double scale, int64_t* hist, hipStream_t stream) {
+  CheckBinned("gbdt histogram multi", m.nnz, m.num_features);
+  CHECK(num_nodes >= 1 && num_nodes <= kGbdtMaxNodes)
+      << "gbdt histogram multi: num_nodes out of range";
+  CHECK(num_outputs >= 1 && num_outputs <= kGbdtMaxOutputs)
+      << "gbdt histogram multi: num_outputs must be in [1, " << kGbdtMaxOutputs << "]";
+  if (m.nnz == 0 || m.total_bins == 0 || m.rows == 0) return;
+  hipLaunchKernelGGL(k_gbdt_hist_multi, dim3(SegmentsOf(m.nnz)), dim3(kThreads), 0, stream, m.offset,
+                     m.row, m.bin, static_cast<int64_t>(m.nnz), static_cast<int64_t>(m.num_features),
+                     m.cut_ptr, static_cast<int64_t>(m.total_bins), grad, hess, pos,
+                     static_cast<int64_t>(m.rows), first_node, static_cast<int32_t>(num_nodes),
+                     static_cast<int32_t>(num_outputs), scale,
+                     reinterpret_cast<unsigned long long*>(hist));
+  DMLC_HIP_CHECK_LAUNCH();
+}
+
+namespace {
+template <int kKp>
+void LaunchSplitScanMulti(dim3 grid, hipStream_t stream, const int64_t* hist, const int64_t* node_sum,
+                          const int64_t* cut_ptr, uint64_t num_features, uint64_t total_bins,
+                          uint32_t num_outputs, double scale, double reg_lambda, double gamma,
+                          double min_hess, void* scratch) {
+  hipLaunchKernelGGL(k_gbdt_split_scan_multi<kKp>, grid, dim3(kThreads), 0, stream,
+                     reinterpret_cast<const long long*>(hist),
+                     reinterpret_cast<const long long*>(node_sum), cut_ptr,
+                     static_cast<int64_t>(num_features), static_cast<int64_t>(total_bins),
+                     static_cast<int32_t>(num_outputs), scale, reg_lambda, gamma, min_hess,
+                     static_cast<Cand*>(scratch));
+}
+}  // namespace
+
+void LaunchGbdtBestSplitsMulti(const int64_t* hist, const int64_t* node_sum, const int64_t* cut_ptr,
+                               uint64_t num_features, uint64_t total_bins, uint32_t num_nodes,
+                               uint32_t num_outputs, double scale, double reg_lambda, double gamma,
+                               double min_child_weight, void* scratch, int64_t* feature, int32_t* bin,
+                               uint8_t* default_left, double* gain, hipStream_t stream) {
+  CheckBinned("gbdt best splits multi", 0, num_features);
+  CHECK(num_nodes <= kGbdtMaxNodes) << "gbdt best splits multi: num_nodes out of range";
+  CHECK(num_outputs >= 1 && num_outputs <= kGbdtMaxOutputs)
+      << "gbdt best splits multi: num_outputs must be in [1, " << kGbdtMaxOutputs << "]";
+  CHECK(reg_lambda > 0.0 && scale > 0.0)
+      << "gbdt best splits multi: reg_lambda and scale must be > 0";
+  CHECK(Aligned16(scratch)) << "gbdt best splits multi: scratch must be 16-byte aligned";
+  if (num_nodes == 0) return;
+  const uint32_t parts = static_cast<uint32_t>((num_features + kThreads - 1) / kThreads);
+  const dim3 grid(parts, num_nodes);
+  const double min_hess = static_cast<double>(num_outputs) * min_child_weight * scale;
+  auto scan = num_outputs <= 1    ? LaunchSplitScanMulti<1>
+              : num_outputs <= 2  ? LaunchSplitScanMulti<2>
+              : num_outputs <= 4  ? LaunchSplitScanMulti<4>
+              : num_outputs <= 8  ? LaunchSplitScanMulti<8>
+              : num_outputs <= 16 ? LaunchSplitScanMulti<16>
+                                  : LaunchSplitScanMulti<32>;
+  static_assert(kGbdtMaxOutputs <= 32, "a group of lanes per (node, feature) is at most half a wave");
+  scan(grid, stream, hist, node_sum, cut_ptr, num_features, total_bins, num_outputs, scale,
+       reg_lambda, gamma, min_hess, scratch);
   DMLC_HIP_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_gbdt_split_pick, dim3(num_nodes), dim3(kThreads), 0, stream,
                      static_cast<const Cand*>(scratch), static_cast<int64_t>(parts), feature, bin,

@@ -45,6 +45,8 @@
  *   GB3 grad histogram   LaunchGbdtHistogram      (gbdt_kernels.hip)
  *   GB4 best splits      LaunchGbdtBestSplits     (gbdt_kernels.hip)
  *   GB5 advance rows     LaunchGbdtAdvance        (gbdt_kernels.hip)
+ *   GB3m K-output histogram LaunchGbdtHistogramMulti (gbdt_kernels.hip)
+ *   GB4m K-output splits LaunchGbdtBestSplitsMulti (gbdt_kernels.hip)
  *   GB6 forest inference LaunchForestPredict      (forest_kernels.hip)
  * The launchers of K9, K11, M1 / M2, FF1 / FF2, G2, GB6 and the transpose take
  * their CSR operand as one CsrView and pick the kernel for its index width
@@ -876,6 +878,30 @@ void LaunchGbdtAdvance(const GbdtBinned& m, const int32_t* pos_in, const int64_t
                        const int32_t* split_bin, const uint8_t* default_left, const int32_t* left,
                        const int32_t* right, int32_t first_node, uint32_t num_nodes, int32_t* pos_out,
                        hipStream_t stream);
+/*! \brief most outputs (values per leaf) of GB3m / GB4m */
+constexpr uint32_t kGbdtMaxOutputs = 32;
+/*!
+ * \brief GB3m: GB3 for grad / hess [rows x num_outputs] (row-major): hist[node,
+ *  cut_ptr[f] + bin, k, :] += (llrint(g[r, k] scale), llrint(h[r, k] scale));
+ *  hist: int64 [num_nodes x total_bins x num_outputs x 2], zeroed by the
+ *  caller.  GB3's rows, rounding and skipping rules; the same bytes on every run.
+ */
+void LaunchGbdtHistogramMulti(const GbdtBinned& m, const float* grad, const float* hess,
+                              const int32_t* pos, int32_t first_node, uint32_t num_nodes,
+                              uint32_t num_outputs, double scale, int64_t* hist, hipStream_t stream);
+/*!
+ * \brief GB4m: GB4 on hist [N x total_bins x K x 2] (GB3m) and node_sum [N x K x
+ *  2], K = num_outputs: the same candidates and tie order, gain = 1/2 sum_k
+ *  (GL_k^2 / (HL_k + l) + GR_k^2 / (HR_k + l) - G_k^2 / (H_k + l)) - gamma,
+ *  valid with sum_k HL_k and sum_k HR_k >= K min_child_weight scale on the
+ *  integer sums.  The float64 sum over k has a fixed order.  scratch:
+ *  GbdtSplitScratchBytes(num_nodes, num_features), as for GB4.
+ */
+void LaunchGbdtBestSplitsMulti(const int64_t* hist, const int64_t* node_sum, const int64_t* cut_ptr,
+                               uint64_t num_features, uint64_t total_bins, uint32_t num_nodes,
+                               uint32_t num_outputs, double scale, double reg_lambda, double gamma,
+                               double min_child_weight, void* scratch, int64_t* feature, int32_t* bin,
+                               uint8_t* default_left, double* gain, hipStream_t stream);
 // ---------------- forest inference on the row CSR (forest_kernels.hip) ----------------
 /*! \brief entries of a row GB6 stages in a wave's LDS slice (8 bytes each); a
  *  longer row is re-staged in chunks of this many at every tree level */
