@@ -1565,6 +1565,85 @@ def gradient_scale(grad: torch.Tensor, hess: torch.Tensor) -> float:
     return math.ldexp(1.0, 61 - (k - 1 if m == 0.5 else k))
 
 
+def _check_outputs(name: str, what: str, t, rows: int, dev, outputs=None) -> int:
+    """``t`` as float32 ``[rows, K]`` gradients; returns K"""
+    kmax = int(_dmlc.gbdt_max_outputs())
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 \
+            or t.shape[0] != rows or t.device != dev or not t.is_contiguous():
+        raise ValueError(f"{name}: {what} must be a contiguous float32 tensor [{rows}, K] on {dev}")
+    k = int(t.shape[1])
+    if not 1 <= k <= kmax or (outputs is not None and k != outputs):
+        raise ValueError(f"{name}: {what} has {k} outputs, expected "
+                         + (f"{outputs}" if outputs is not None else f"1 to {kmax}"))
+    return k
+
+
+def _grad_histogram(name: str, vector: bool, binned, grad, hess, pos, num_nodes, scale, first_node):
+    """GB3 on ``[rows]`` gradients, or with ``vector`` GB3m on ``[rows, K]``, for the public
+    function ``name``"""
+    arg = _binned_arg(name, binned)
+    _check_window(name, num_nodes, first_node)
+    rows, total, dev = arg[6], arg[7], binned["row"].device
+    if vector:
+        k = _check_outputs(name, "grad", grad, rows, dev)
+        _check_outputs(name, "hess", hess, rows, dev, k)
+    else:
+        k = int(_dmlc.gbdt_scalar)
+        _check_rows(name, "grad", grad, torch.float32, rows, dev)
+        _check_rows(name, "hess", hess, torch.float32, rows, dev)
+    _check_rows(name, "pos", pos, torch.int32, rows, dev)
+    if not float(scale) > 0:
+        raise ValueError(f"{name}: scale must be > 0, got {scale!r}")
+    shape = (num_nodes, total, k, 2) if vector else (num_nodes, total, 2)
+    hist = torch.zeros(shape, dtype=torch.int64, device=dev)
+    if rows > 0 and total > 0 and arg[5] > 0:
+        _dmlc.gbdt_histogram(arg, _ptr(grad), _ptr(hess), _ptr(pos), first_node, num_nodes, k,
+                             float(scale), _ptr(hist), _stream())
+    return hist
+
+
+def _best_splits(name: str, vector: bool, hist, node_sum, cut_ptr, scale, reg_lambda, gamma,
+                 min_child_weight) -> Dict:
+    """GB4 on ``hist`` ``[N, bins, 2]``, or with ``vector`` GB4m on ``[N, bins, K, 2]``, for the
+    public function ``name``"""
+    kmax = int(_dmlc.gbdt_max_outputs())
+    if not isinstance(hist, torch.Tensor) or hist.dtype != torch.int64 \
+            or hist.dim() != (4 if vector else 3) or hist.shape[-1] != 2 \
+            or (vector and not 1 <= hist.shape[2] <= kmax) or not hist.is_cuda \
+            or not hist.is_contiguous():
+        raise ValueError(f"{name}: hist must be a contiguous int64 device tensor "
+                         + (f"[N, bins, K, 2], K in [1, {kmax}]" if vector else "[N, bins, 2]"))
+    n, total, dev = int(hist.shape[0]), int(hist.shape[1]), hist.device
+    k = int(hist.shape[2]) if vector else int(_dmlc.gbdt_scalar)
+    sums = (n, k, 2) if vector else (n, 2)
+    if not isinstance(node_sum, torch.Tensor) or node_sum.dtype != torch.int64 \
+            or tuple(node_sum.shape) != sums or node_sum.device != dev \
+            or not node_sum.is_contiguous():
+        raise ValueError(f"{name}: node_sum must be a contiguous int64 tensor {list(sums)} on {dev}")
+    if not isinstance(cut_ptr, torch.Tensor) or cut_ptr.dtype != torch.int64 or cut_ptr.dim() != 1 \
+            or cut_ptr.numel() < 2 or cut_ptr.device != dev or not cut_ptr.is_contiguous():
+        raise ValueError(f"{name}: cut_ptr must be a contiguous int64 tensor [F + 1] on {dev}")
+    if not float(reg_lambda) > 0:
+        raise ValueError(f"{name}: reg_lambda must be > 0, got {reg_lambda!r}")
+    if not float(scale) > 0:
+        raise ValueError(f"{name}: scale must be > 0, got {scale!r}")
+    if n > int(_dmlc.gbdt_max_nodes()):
+        raise ValueError(f"{name}: at most {int(_dmlc.gbdt_max_nodes())} nodes, got {n}")
+    nfeat = cut_ptr.numel() - 1
+    res = {"feature": torch.full((n,), -1, dtype=torch.int64, device=dev),
+           "bin": torch.zeros(n, dtype=torch.int32, device=dev),
+           "default_left": torch.zeros(n, dtype=torch.bool, device=dev),
+           "gain": torch.zeros(n, dtype=torch.float64, device=dev)}
+    if n > 0:
+        ws = _workspace(int(_dmlc.gbdt_split_scratch_bytes(n, nfeat)) + 16, dev)
+        _dmlc.gbdt_best_splits(_ptr(hist), _ptr(node_sum), _ptr(cut_ptr), nfeat, total, n, k,
+                               float(scale), float(reg_lambda), float(gamma),
+                               float(min_child_weight), (_ptr(ws) + 15) // 16 * 16,
+                               _ptr(res["feature"]), _ptr(res["bin"]), _ptr(res["default_left"]),
+                               _ptr(res["gain"]), _stream())
+    return res
+
+
 def grad_histogram(binned: Dict, grad: torch.Tensor, hess: torch.Tensor, pos: torch.Tensor,
                    num_nodes: int, scale: float, first_node: int = 0) -> torch.Tensor:
     """The gradient histograms of ``num_nodes`` tree nodes (GB3), int64
@@ -1582,19 +1661,7 @@ def grad_histogram(binned: Dict, grad: torch.Tensor, hess: torch.Tensor, pos: to
     writes each cell once: by a plain store for a column inside one segment,
     by one 64-bit atomic per non-zero cell for a column that spans several.
     Nothing is read back."""
-    arg = _binned_arg("grad_histogram", binned)
-    _check_window("grad_histogram", num_nodes, first_node)
-    rows, total, dev = arg[6], arg[7], binned["row"].device
-    _check_rows("grad_histogram", "grad", grad, torch.float32, rows, dev)
-    _check_rows("grad_histogram", "hess", hess, torch.float32, rows, dev)
-    _check_rows("grad_histogram", "pos", pos, torch.int32, rows, dev)
-    if not float(scale) > 0:
-        raise ValueError(f"grad_histogram: scale must be > 0, got {scale!r}")
-    hist = torch.zeros((num_nodes, total, 2), dtype=torch.int64, device=dev)
-    if rows > 0 and total > 0 and arg[5] > 0:
-        _dmlc.gbdt_histogram(arg, _ptr(grad), _ptr(hess), _ptr(pos), first_node, num_nodes,
-                             float(scale), _ptr(hist), _stream())
-    return hist
+    return _grad_histogram("grad_histogram", False, binned, grad, hess, pos, num_nodes, scale, first_node)
 
 
 def best_splits(hist: torch.Tensor, node_sum: torch.Tensor, cut_ptr: torch.Tensor, scale: float,
@@ -1616,49 +1683,8 @@ def best_splits(hist: torch.Tensor, node_sum: torch.Tensor, cut_ptr: torch.Tenso
     the lowest (feature, bin), then to missing-right -- a total order, so
     every run gives the same answer.  The float threshold of a split is
     ``cut[cut_ptr[feature] + bin]``.  ``reg_lambda`` must be > 0."""
-    if not isinstance(hist, torch.Tensor) or hist.dtype != torch.int64 or hist.dim() != 3 \
-            or hist.shape[2] != 2 or not hist.is_cuda or not hist.is_contiguous():
-        raise ValueError("best_splits: hist must be a contiguous int64 device tensor [N, bins, 2]")
-    n, total, dev = int(hist.shape[0]), int(hist.shape[1]), hist.device
-    if not isinstance(node_sum, torch.Tensor) or node_sum.dtype != torch.int64 \
-            or tuple(node_sum.shape) != (n, 2) or node_sum.device != dev \
-            or not node_sum.is_contiguous():
-        raise ValueError(f"best_splits: node_sum must be a contiguous int64 tensor [{n}, 2] on {dev}")
-    if not isinstance(cut_ptr, torch.Tensor) or cut_ptr.dtype != torch.int64 or cut_ptr.dim() != 1 \
-            or cut_ptr.numel() < 2 or cut_ptr.device != dev or not cut_ptr.is_contiguous():
-        raise ValueError(f"best_splits: cut_ptr must be a contiguous int64 tensor [F + 1] on {dev}")
-    if not float(reg_lambda) > 0:
-        raise ValueError(f"best_splits: reg_lambda must be > 0, got {reg_lambda!r}")
-    if not float(scale) > 0:
-        raise ValueError(f"best_splits: scale must be > 0, got {scale!r}")
-    if n > int(_dmlc.gbdt_max_nodes()):
-        raise ValueError(f"best_splits: at most {int(_dmlc.gbdt_max_nodes())} nodes, got {n}")
-    nfeat = cut_ptr.numel() - 1
-    res = {"feature": torch.full((n,), -1, dtype=torch.int64, device=dev),
-           "bin": torch.zeros(n, dtype=torch.int32, device=dev),
-           "default_left": torch.zeros(n, dtype=torch.bool, device=dev),
-           "gain": torch.zeros(n, dtype=torch.float64, device=dev)}
-    if n > 0:
-        ws = _workspace(int(_dmlc.gbdt_split_scratch_bytes(n, nfeat)) + 16, dev)
-        _dmlc.gbdt_best_splits(_ptr(hist), _ptr(node_sum), _ptr(cut_ptr), nfeat, total, n,
-                               float(scale), float(reg_lambda), float(gamma),
-                               float(min_child_weight), (_ptr(ws) + 15) // 16 * 16,
-                               _ptr(res["feature"]), _ptr(res["bin"]), _ptr(res["default_left"]),
-                               _ptr(res["gain"]), _stream())
-    return res
-
-
-def _check_outputs(name: str, what: str, t, rows: int, dev, outputs=None) -> int:
-    """``t`` as float32 ``[rows, K]`` gradients; returns K"""
-    kmax = int(_dmlc.gbdt_max_outputs())
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 \
-            or t.shape[0] != rows or t.device != dev or not t.is_contiguous():
-        raise ValueError(f"{name}: {what} must be a contiguous float32 tensor [{rows}, K] on {dev}")
-    k = int(t.shape[1])
-    if not 1 <= k <= kmax or (outputs is not None and k != outputs):
-        raise ValueError(f"{name}: {what} has {k} outputs, expected "
-                         + (f"{outputs}" if outputs is not None else f"1 to {kmax}"))
-    return k
+    return _best_splits("best_splits", False, hist, node_sum, cut_ptr, scale, reg_lambda, gamma,
+                        min_child_weight)
 
 
 def grad_histogram_multi(binned: Dict, grad: torch.Tensor, hess: torch.Tensor, pos: torch.Tensor,
@@ -1676,20 +1702,8 @@ def grad_histogram_multi(binned: Dict, grad: torch.Tensor, hess: torch.Tensor, p
     as one contiguous piece.  The LDS table tiles the nodes, and for a column
     too wide for all K outputs of one node the outputs.  Integer sums: the
     same bytes on every run.  Nothing is read back."""
-    name = "grad_histogram_multi"
-    arg = _binned_arg(name, binned)
-    _check_window(name, num_nodes, first_node)
-    rows, total, dev = arg[6], arg[7], binned["row"].device
-    k = _check_outputs(name, "grad", grad, rows, dev)
-    _check_outputs(name, "hess", hess, rows, dev, k)
-    _check_rows(name, "pos", pos, torch.int32, rows, dev)
-    if not float(scale) > 0:
-        raise ValueError(f"{name}: scale must be > 0, got {scale!r}")
-    hist = torch.zeros((num_nodes, total, k, 2), dtype=torch.int64, device=dev)
-    if rows > 0 and total > 0 and arg[5] > 0:
-        _dmlc.gbdt_histogram_multi(arg, _ptr(grad), _ptr(hess), _ptr(pos), first_node, num_nodes, k,
-                                   float(scale), _ptr(hist), _stream())
-    return hist
+    return _grad_histogram("grad_histogram_multi", True, binned, grad, hess, pos, num_nodes, scale,
+                           first_node)
 
 
 def best_splits_multi(hist: torch.Tensor, node_sum: torch.Tensor, cut_ptr: torch.Tensor,
@@ -1706,40 +1720,8 @@ def best_splits_multi(hist: torch.Tensor, node_sum: torch.Tensor, cut_ptr: torch
     per output.  A group of lanes owns a (node, feature), one lane per
     output, and the sum over k is a shuffle butterfly in a fixed order: two
     calls give the same bytes."""
-    name = "best_splits_multi"
-    kmax = int(_dmlc.gbdt_max_outputs())
-    if not isinstance(hist, torch.Tensor) or hist.dtype != torch.int64 or hist.dim() != 4 \
-            or hist.shape[3] != 2 or not 1 <= hist.shape[2] <= kmax or not hist.is_cuda \
-            or not hist.is_contiguous():
-        raise ValueError(f"{name}: hist must be a contiguous int64 device tensor [N, bins, K, 2], "
-                         f"K in [1, {kmax}]")
-    n, total, k, dev = int(hist.shape[0]), int(hist.shape[1]), int(hist.shape[2]), hist.device
-    if not isinstance(node_sum, torch.Tensor) or node_sum.dtype != torch.int64 \
-            or tuple(node_sum.shape) != (n, k, 2) or node_sum.device != dev \
-            or not node_sum.is_contiguous():
-        raise ValueError(f"{name}: node_sum must be a contiguous int64 tensor [{n}, {k}, 2] on {dev}")
-    if not isinstance(cut_ptr, torch.Tensor) or cut_ptr.dtype != torch.int64 or cut_ptr.dim() != 1 \
-            or cut_ptr.numel() < 2 or cut_ptr.device != dev or not cut_ptr.is_contiguous():
-        raise ValueError(f"{name}: cut_ptr must be a contiguous int64 tensor [F + 1] on {dev}")
-    if not float(reg_lambda) > 0:
-        raise ValueError(f"{name}: reg_lambda must be > 0, got {reg_lambda!r}")
-    if not float(scale) > 0:
-        raise ValueError(f"{name}: scale must be > 0, got {scale!r}")
-    if n > int(_dmlc.gbdt_max_nodes()):
-        raise ValueError(f"{name}: at most {int(_dmlc.gbdt_max_nodes())} nodes, got {n}")
-    nfeat = cut_ptr.numel() - 1
-    res = {"feature": torch.full((n,), -1, dtype=torch.int64, device=dev),
-           "bin": torch.zeros(n, dtype=torch.int32, device=dev),
-           "default_left": torch.zeros(n, dtype=torch.bool, device=dev),
-           "gain": torch.zeros(n, dtype=torch.float64, device=dev)}
-    if n > 0:
-        ws = _workspace(int(_dmlc.gbdt_split_scratch_bytes(n, nfeat)) + 16, dev)
-        _dmlc.gbdt_best_splits_multi(_ptr(hist), _ptr(node_sum), _ptr(cut_ptr), nfeat, total, n, k,
-                                     float(scale), float(reg_lambda), float(gamma),
-                                     float(min_child_weight), (_ptr(ws) + 15) // 16 * 16,
-                                     _ptr(res["feature"]), _ptr(res["bin"]),
-                                     _ptr(res["default_left"]), _ptr(res["gain"]), _stream())
-    return res
+    return _best_splits("best_splits_multi", True, hist, node_sum, cut_ptr, scale, reg_lambda, gamma,
+                        min_child_weight)
 
 
 def advance_rows(binned: Dict, pos: torch.Tensor, split: Dict, left: torch.Tensor,

@@ -22,7 +22,10 @@
  *  GB3m k_gbdt_hist_multi, GB4m k_gbdt_split_scan_multi: GB3 / GB4 for trees
  *                      with K values per leaf (K gradients per row): a group of
  *                      lanes per entry / per (node, feature), one lane per
- *                      output; described at the kernels.
+ *                      output; described at the kernels.  Each pair has one
+ *                      launcher, which picks the kernel by its num_outputs
+ *                      (kGbdtScalar: GB3 / GB4), and shares its cell arithmetic
+ *                      (add_to_cell, flush_cell) and candidate key (split_key).
  *
  *  Segments.  The entries of the column-major matrix, in storage order, are
  *  cut every kGbdtSegmentEntries: workgroup s owns entries [s S, (s + 1) S).
@@ -162,6 +165,29 @@ __device__ __forceinline__ int64_t group_end(const int64_t* __restrict__ cut_ptr
     if (fb <= fa) fb = fa + 1;
   }
   return block_bcast(fb, slot);
+}
+
+/*! \brief GB3 / GB3m: the quantised (g, h) of an entry's row added to cell `at` of the LDS table */
+__device__ __forceinline__ void add_to_cell(unsigned long long* table, int64_t at, float g, float h,
+                                            double scale) {
+  const long long qg = __double2ll_rn(static_cast<double>(g) * scale);
+  const long long qh = __double2ll_rn(static_cast<double>(h) * scale);
+  unsigned long long* const cell = table + 2 * at;
+  atomicAdd(cell, static_cast<unsigned long long>(qg));
+  atomicAdd(cell + 1, static_cast<unsigned long long>(qh));
+}
+
+/*! \brief GB3 / GB3m: a finished cell to the histogram: plain stores where this segment owns the
+ *  bin's column, else one 64-bit atomic per non-zero value */
+__device__ __forceinline__ void flush_cell(unsigned long long* dst, unsigned long long g,
+                                           unsigned long long h, bool owned) {
+  if (owned) {
+    dst[0] = g;
+    dst[1] = h;
+  } else {
+    if (g != 0ull) atomicAdd(dst, g);
+    if (h != 0ull) atomicAdd(dst + 1, h);
+  }
 }
 
 /*! \brief the float whose order-preserving u32 is u */
@@ -322,11 +348,7 @@ __global__ __launch_bounds__(kThreads) void k_gbdt_hist(
           if (cl < 0 || b >= nc || cl + b >= width || r >= static_cast<uint64_t>(rows)) continue;
           const int64_t node = static_cast<int64_t>(pos[r]) - first_node - n0;
           if (node < 0 || node >= nn) continue;
-          const long long qg = __double2ll_rn(static_cast<double>(grad[r]) * scale);
-          const long long qh = __double2ll_rn(static_cast<double>(hess[r]) * scale);
-          unsigned long long* const cell = s_acc + 2 * (node * width + cl + b);
-          atomicAdd(cell, static_cast<unsigned long long>(qg));
-          atomicAdd(cell + 1, static_cast<unsigned long long>(qh));
+          add_to_cell(s_acc, node * width + cl + b, grad[r], hess[r], scale);
         }
         __syncthreads();
         const uint32_t width32 = static_cast<uint32_t>(width);  // cells <= kGbdtCells
@@ -334,13 +356,7 @@ __global__ __launch_bounds__(kThreads) void k_gbdt_hist(
           const int64_t node = i / width32, gb = c0 + i % width32;
           const unsigned long long g = s_acc[2 * i], h = s_acc[2 * i + 1];
           unsigned long long* const dst = hist + 2 * ((n0 + node) * total_bins + gb);
-          if (gb >= head_end && gb < tail_begin) {
-            dst[0] = g;
-            dst[1] = h;
-          } else {
-            if (g != 0ull) atomicAdd(dst, g);
-            if (h != 0ull) atomicAdd(dst + 1, h);
-          }
+          flush_cell(dst, g, h, gb >= head_end && gb < tail_begin);
         }
         __syncthreads();
       }
@@ -360,6 +376,12 @@ constexpr unsigned long long kNoKey = ~0ull;
 /*! \brief a total order: the greater gain, then the lower (feature, bin), then missing-right */
 __device__ __forceinline__ Cand better(const Cand& a, const Cand& b) {
   return (a.gain > b.gain || (a.gain == b.gain && a.key < b.key)) ? a : b;
+}
+
+/*! \brief GB4 / GB4m: Cand::key of feature f, bin t and missing-left dir */
+__device__ __forceinline__ unsigned long long split_key(int64_t f, int64_t t, int dir) {
+  return (static_cast<unsigned long long>(f) << 9) | (static_cast<unsigned long long>(t) << 1) |
+         static_cast<unsigned long long>(dir);
 }
 
 /*! \brief the workgroup's best candidate, in thread 0 */
@@ -418,12 +440,7 @@ __global__ __launch_bounds__(kThreads) void k_gbdt_split_scan(
           if (!(hl >= min_child_weight && hr >= min_child_weight)) continue;
           const double gain =
               0.5 * (gl * gl / (hl + reg_lambda) + gr * gr / (hr + reg_lambda) - parent) - gamma;
-          if (gain > 0.0) {
-            const unsigned long long key = (static_cast<unsigned long long>(f) << 9) |
-                                           (static_cast<unsigned long long>(t) << 1) |
-                                           static_cast<unsigned long long>(dir);
-            best = better(best, Cand{gain, key});
-          }
+          if (gain > 0.0) best = better(best, Cand{gain, split_key(f, t, dir)});
         }
       }
     }
@@ -565,11 +582,7 @@ __global__ __launch_bounds__(kThreads) void k_gbdt_hist_multi(
               const int64_t node = static_cast<int64_t>(pos[r]) - first_node - n0;
               if (node < 0 || node >= nn) continue;
               const int64_t at = static_cast<int64_t>(r) * K + k0 + lane;
-              const long long qg = __double2ll_rn(static_cast<double>(grad[at]) * scale);
-              const long long qh = __double2ll_rn(static_cast<double>(hess[at]) * scale);
-              unsigned long long* const cell = s_acc + 2 * ((node * width + cl + b) * kk + lane);
-              atomicAdd(cell, static_cast<unsigned long long>(qg));
-              atomicAdd(cell + 1, static_cast<unsigned long long>(qh));
+              add_to_cell(s_acc, (node * width + cl + b) * kk + lane, grad[at], hess[at], scale);
             }
           }
           __syncthreads();
@@ -581,13 +594,7 @@ __global__ __launch_bounds__(kThreads) void k_gbdt_hist_multi(
             const unsigned long long g = s_acc[2 * i], h = s_acc[2 * i + 1];
             unsigned long long* const dst =
                 hist + 2 * (((n0 + node) * total_bins + gb) * K + k0 + k);
-            if (gb >= head_end && gb < tail_begin) {
-              dst[0] = g;
-              dst[1] = h;
-            } else {
-              if (g != 0ull) atomicAdd(dst, g);
-              if (h != 0ull) atomicAdd(dst + 1, h);
-            }
+            flush_cell(dst, g, h, gb >= head_end && gb < tail_begin);
           }
           __syncthreads();
         }
@@ -684,12 +691,7 @@ __global__ __launch_bounds__(kThreads) void k_gbdt_split_scan_multi(
         if (!(static_cast<double>(hl) >= min_hess && static_cast<double>(nh_all - hl) >= min_hess))
           continue;
         const double gain = 0.5 * (dir != 0 ? sum_left : sum_right) - gamma;
-        if (gain > 0.0) {
-          const unsigned long long key = (static_cast<unsigned long long>(f) << 9) |
-                                         (static_cast<unsigned long long>(t) << 1) |
-                                         static_cast<unsigned long long>(dir);
-          best = better(best, Cand{gain, key});
-        }
+        if (gain > 0.0) best = better(best, Cand{gain, split_key(f, t, dir)});
       }
     }
   }
@@ -703,6 +705,15 @@ void CheckBinned(const char* op, uint64_t nnz, uint64_t num_features) {
   CHECK(num_features >= 1 && num_features <= CSRTransposeMaxFeatures())
       << op << ": num_features must be in [1, " << CSRTransposeMaxFeatures() << "]";
   CHECK_LT(nnz, (1ull << 31) * kSeg) << op << ": too many entries";
+}
+
+/*! \brief what the histogram and the split search check alike, in either layout */
+void CheckLevel(const char* op, uint64_t nnz, uint64_t num_features, bool nodes_in_range,
+                uint32_t num_outputs) {
+  CheckBinned(op, nnz, num_features);
+  CHECK(nodes_in_range) << op << ": num_nodes out of range";
+  CHECK(num_outputs == kGbdtScalar || num_outputs <= kGbdtMaxOutputs)
+      << op << ": num_outputs must be in [1, " << kGbdtMaxOutputs << "]";
 }
 }  // namespace
 
@@ -746,16 +757,25 @@ void LaunchGbdtBin(const CsrView& columns, uint64_t nnz, const int64_t* cut_ptr,
 }
 
 void LaunchGbdtHistogram(const GbdtBinned& m, const float* grad, const float* hess,
-                         const int32_t* pos, int32_t first_node, uint32_t num_nodes, double scale,
-                         int64_t* hist, hipStream_t stream) {
-  CheckBinned("gbdt histogram", m.nnz, m.num_features);
-  CHECK(num_nodes >= 1 && num_nodes <= kGbdtMaxNodes) << "gbdt histogram: num_nodes out of range";
+                         const int32_t* pos, int32_t first_node, uint32_t num_nodes,
+                         uint32_t num_outputs, double scale, int64_t* hist, hipStream_t stream) {
+  const bool scalar = num_outputs == kGbdtScalar;
+  CheckLevel(scalar ? "gbdt histogram" : "gbdt histogram multi", m.nnz, m.num_features,
+             num_nodes >= 1 && num_nodes <= kGbdtMaxNodes, num_outputs);
   if (m.nnz == 0 || m.total_bins == 0 || m.rows == 0) return;
-  hipLaunchKernelGGL(k_gbdt_hist, dim3(SegmentsOf(m.nnz)), dim3(kThreads), 0, stream, m.offset, m.row,
-                     m.bin, static_cast<int64_t>(m.nnz), static_cast<int64_t>(m.num_features),
-                     m.cut_ptr, static_cast<int64_t>(m.total_bins), grad, hess, pos,
-                     static_cast<int64_t>(m.rows), first_node, static_cast<int32_t>(num_nodes), scale,
-                     reinterpret_cast<unsigned long long*>(hist));
+  const dim3 grid(SegmentsOf(m.nnz)), block(kThreads);
+  const int64_t nnz = static_cast<int64_t>(m.nnz), nfeat = static_cast<int64_t>(m.num_features);
+  const int64_t total = static_cast<int64_t>(m.total_bins), rows = static_cast<int64_t>(m.rows);
+  const int32_t nodes = static_cast<int32_t>(num_nodes);
+  unsigned long long* const out = reinterpret_cast<unsigned long long*>(hist);
+  if (scalar) {
+    hipLaunchKernelGGL(k_gbdt_hist, grid, block, 0, stream, m.offset, m.row, m.bin, nnz, nfeat,
+                       m.cut_ptr, total, grad, hess, pos, rows, first_node, nodes, scale, out);
+  } else {
+    hipLaunchKernelGGL(k_gbdt_hist_multi, grid, block, 0, stream, m.offset, m.row, m.bin, nnz, nfeat,
+                       m.cut_ptr, total, grad, hess, pos, rows, first_node, nodes,
+                       static_cast<int32_t>(num_outputs), scale, out);
+  }
   DMLC_HIP_CHECK_LAUNCH();
 }
 
@@ -764,90 +784,40 @@ size_t GbdtSplitScratchBytes(uint64_t num_nodes, uint64_t num_features) {
 }
 
 void LaunchGbdtBestSplits(const int64_t* hist, const int64_t* node_sum, const int64_t* cut_ptr,
-                          uint64_t num_features, uint64_t total_bins, uint32_t num_nodes, double scale,
-                          double reg_lambda, double gamma, double min_child_weight, void* scratch,
-                          int64_t* feature, int32_t* bin, uint8_t* default_left, double* gain,
-                          hipStream_t stream) {
-  CheckBinned("gbdt best splits", 0, num_features);
-  CHECK(num_nodes <= kGbdtMaxNodes) << "gbdt best splits: num_nodes out of range";
-  CHECK(reg_lambda > 0.0 && scale > 0.0) << "gbdt best splits: reg_lambda and scale must be > 0";
-  CHECK(Aligned16(scratch)) << "gbdt best splits: scratch must be 16-byte aligned";
-  if (num_nodes == 0) return;
-  const uint32_t parts = static_cast<uint32_t>((num_features + kThreads - 1) / kThreads);
-  hipLaunchKernelGGL(k_gbdt_split_scan, dim3(parts, num_nodes), dim3(kThreads), 0, stream,
-                     reinterpret_cast<const long long*>(hist),
-                     reinterpret_cast<const long long*>(node_sum), cut_ptr,
-                     static_cast<int64_t>(num_features), static_cast<int64_t>(total_bins), scale,
-                     reg_lambda, gamma, min_child_weight, static_cast<Cand*>(scratch));
-  DMLC_HIP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_gbdt_split_pick, dim3(num_nodes), dim3(kThreads), 0, stream,
-                     static_cast<const Cand*>(scratch), static_cast<int64_t>(parts), feature, bin,
-                     default_left, gain);
-  DMLC_HIP_CHECK_LAUNCH();
-}
-
-void LaunchGbdtHistogramMulti(const GbdtBinned& m, const float* grad, const float* hess,
-                              const int32_t* pos, int32_t first_node, uint32_t num_nodes,
-                              uint32_t num_outputs, double scale, int64_t* hist, hipStream_t stream) {
-  CheckBinned("gbdt histogram multi", m.nnz, m.num_features);
-  CHECK(num_nodes >= 1 && num_nodes <= kGbdtMaxNodes)
-      << "gbdt histogram multi: num_nodes out of range";
-  CHECK(num_outputs >= 1 && num_outputs <= kGbdtMaxOutputs)
-      << "gbdt histogram multi: num_outputs must be in [1, " << kGbdtMaxOutputs << "]";
-  if (m.nnz == 0 || m.total_bins == 0 || m.rows == 0) return;
-  hipLaunchKernelGGL(k_gbdt_hist_multi, dim3(SegmentsOf(m.nnz)), dim3(kThreads), 0, stream, m.offset,
-                     m.row, m.bin, static_cast<int64_t>(m.nnz), static_cast<int64_t>(m.num_features),
-                     m.cut_ptr, static_cast<int64_t>(m.total_bins), grad, hess, pos,
-                     static_cast<int64_t>(m.rows), first_node, static_cast<int32_t>(num_nodes),
-                     static_cast<int32_t>(num_outputs), scale,
-                     reinterpret_cast<unsigned long long*>(hist));
-  DMLC_HIP_CHECK_LAUNCH();
-}
-
-namespace {
-template <int kKp>
-void LaunchSplitScanMulti(dim3 grid, hipStream_t stream, const int64_t* hist, const int64_t* node_sum,
-                          const int64_t* cut_ptr, uint64_t num_features, uint64_t total_bins,
+                          uint64_t num_features, uint64_t total_bins, uint32_t num_nodes,
                           uint32_t num_outputs, double scale, double reg_lambda, double gamma,
-                          double min_hess, void* scratch) {
-  hipLaunchKernelGGL(k_gbdt_split_scan_multi<kKp>, grid, dim3(kThreads), 0, stream,
-                     reinterpret_cast<const long long*>(hist),
-                     reinterpret_cast<const long long*>(node_sum), cut_ptr,
-                     static_cast<int64_t>(num_features), static_cast<int64_t>(total_bins),
-                     static_cast<int32_t>(num_outputs), scale, reg_lambda, gamma, min_hess,
-                     static_cast<Cand*>(scratch));
-}
-}  // namespace
-
-void LaunchGbdtBestSplitsMulti(const int64_t* hist, const int64_t* node_sum, const int64_t* cut_ptr,
-                               uint64_t num_features, uint64_t total_bins, uint32_t num_nodes,
-                               uint32_t num_outputs, double scale, double reg_lambda, double gamma,
-                               double min_child_weight, void* scratch, int64_t* feature, int32_t* bin,
-                               uint8_t* default_left, double* gain, hipStream_t stream) {
-  CheckBinned("gbdt best splits multi", 0, num_features);
-  CHECK(num_nodes <= kGbdtMaxNodes) << "gbdt best splits multi: num_nodes out of range";
-  CHECK(num_outputs >= 1 && num_outputs <= kGbdtMaxOutputs)
-      << "gbdt best splits multi: num_outputs must be in [1, " << kGbdtMaxOutputs << "]";
-  CHECK(reg_lambda > 0.0 && scale > 0.0)
-      << "gbdt best splits multi: reg_lambda and scale must be > 0";
-  CHECK(Aligned16(scratch)) << "gbdt best splits multi: scratch must be 16-byte aligned";
+                          double min_child_weight, void* scratch, int64_t* feature, int32_t* bin,
+                          uint8_t* default_left, double* gain, hipStream_t stream) {
+  const bool scalar = num_outputs == kGbdtScalar;
+  const char* const op = scalar ? "gbdt best splits" : "gbdt best splits multi";
+  CheckLevel(op, 0, num_features, num_nodes <= kGbdtMaxNodes, num_outputs);
+  CHECK(reg_lambda > 0.0 && scale > 0.0) << op << ": reg_lambda and scale must be > 0";
+  CHECK(Aligned16(scratch)) << op << ": scratch must be 16-byte aligned";
   if (num_nodes == 0) return;
   const uint32_t parts = static_cast<uint32_t>((num_features + kThreads - 1) / kThreads);
-  const dim3 grid(parts, num_nodes);
-  const double min_hess = static_cast<double>(num_outputs) * min_child_weight * scale;
-  auto scan = num_outputs <= 1    ? LaunchSplitScanMulti<1>
-              : num_outputs <= 2  ? LaunchSplitScanMulti<2>
-              : num_outputs <= 4  ? LaunchSplitScanMulti<4>
-              : num_outputs <= 8  ? LaunchSplitScanMulti<8>
-              : num_outputs <= 16 ? LaunchSplitScanMulti<16>
-                                  : LaunchSplitScanMulti<32>;
-  static_assert(kGbdtMaxOutputs <= 32, "a group of lanes per (node, feature) is at most half a wave");
-  scan(grid, stream, hist, node_sum, cut_ptr, num_features, total_bins, num_outputs, scale,
-       reg_lambda, gamma, min_hess, scratch);
+  const dim3 grid(parts, num_nodes), block(kThreads);
+  const long long* const h = reinterpret_cast<const long long*>(hist);
+  const long long* const sums = reinterpret_cast<const long long*>(node_sum);
+  const int64_t nfeat = static_cast<int64_t>(num_features), total = static_cast<int64_t>(total_bins);
+  Cand* const partial = static_cast<Cand*>(scratch);
+  if (scalar) {
+    hipLaunchKernelGGL(k_gbdt_split_scan, grid, block, 0, stream, h, sums, cut_ptr, nfeat, total,
+                       scale, reg_lambda, gamma, min_child_weight, partial);
+  } else {
+    static_assert(kGbdtMaxOutputs <= 32, "a group of lanes per (node, feature) is at most half a wave");
+    auto scan = num_outputs <= 1    ? k_gbdt_split_scan_multi<1>
+                : num_outputs <= 2  ? k_gbdt_split_scan_multi<2>
+                : num_outputs <= 4  ? k_gbdt_split_scan_multi<4>
+                : num_outputs <= 8  ? k_gbdt_split_scan_multi<8>
+                : num_outputs <= 16 ? k_gbdt_split_scan_multi<16>
+                                    : k_gbdt_split_scan_multi<32>;
+    const double min_hess = static_cast<double>(num_outputs) * min_child_weight * scale;
+    hipLaunchKernelGGL(scan, grid, block, 0, stream, h, sums, cut_ptr, nfeat, total,
+                       static_cast<int32_t>(num_outputs), scale, reg_lambda, gamma, min_hess, partial);
+  }
   DMLC_HIP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_gbdt_split_pick, dim3(num_nodes), dim3(kThreads), 0, stream,
-                     static_cast<const Cand*>(scratch), static_cast<int64_t>(parts), feature, bin,
-                     default_left, gain);
+  hipLaunchKernelGGL(k_gbdt_split_pick, dim3(num_nodes), block, 0, stream, partial,
+                     static_cast<int64_t>(parts), feature, bin, default_left, gain);
   DMLC_HIP_CHECK_LAUNCH();
 }
 

@@ -42,11 +42,9 @@
  *   L1 lazy row update   LaunchLazyUpdate         (optim_kernels.hip)
  *   GB1 quantile cuts    LaunchGbdtCutCount, LaunchGbdtCutEmit (gbdt_kernels.hip)
  *   GB2 bin features     LaunchGbdtBin            (gbdt_kernels.hip)
- *   GB3 grad histogram   LaunchGbdtHistogram      (gbdt_kernels.hip)
- *   GB4 best splits      LaunchGbdtBestSplits     (gbdt_kernels.hip)
+ *   GB3 / GB3m grad histogram LaunchGbdtHistogram (gbdt_kernels.hip)
+ *   GB4 / GB4m best splits    LaunchGbdtBestSplits (gbdt_kernels.hip)
  *   GB5 advance rows     LaunchGbdtAdvance        (gbdt_kernels.hip)
- *   GB3m K-output histogram LaunchGbdtHistogramMulti (gbdt_kernels.hip)
- *   GB4m K-output splits LaunchGbdtBestSplitsMulti (gbdt_kernels.hip)
  *   GB6 forest inference LaunchForestPredict      (forest_kernels.hip)
  * The launchers of K9, K11, M1 / M2, FF1 / FF2, G2, GB6 and the transpose take
  * their CSR operand as one CsrView and pick the kernel for its index width
@@ -842,31 +840,42 @@ void LaunchGbdtCutEmit(const int64_t* keys, const CsrView& columns, uint64_t nnz
  */
 void LaunchGbdtBin(const CsrView& columns, uint64_t nnz, const int64_t* cut_ptr, const float* cut,
                    int32_t* row_out, uint8_t* bin_out, uint32_t* error, hipStream_t stream);
+/*! \brief most outputs (values per leaf) of GB3m / GB4m */
+constexpr uint32_t kGbdtMaxOutputs = 32;
+/*! \brief num_outputs of the scalar layout: grad / hess [rows], hist [N x total_bins x 2],
+ *  node_sum [N x 2], kernels GB3 / GB4.  1 .. kGbdtMaxOutputs = K is the K-channel layout: grad /
+ *  hess [rows x K] (row-major), hist [N x total_bins x K x 2], node_sum [N x K x 2], kernels
+ *  GB3m / GB4m -- for K = 1 too: the layouts are then the same bytes, the kernels are not. */
+constexpr uint32_t kGbdtScalar = 0;
 /*!
- * \brief GB3: hist[node, cut_ptr[f] + bin, :] += (llrint(g[r] scale), llrint(h[r]
- *  scale)) over the entries (r, bin) of every column f, node = pos[r] -
- *  first_node in [0, num_nodes) (other rows are skipped); hist: int64
- *  [num_nodes x total_bins x 2], zeroed by the caller.  Sums are formed in LDS
- *  per segment; integer sums: the same bytes on every run.
+ * \brief GB3 / GB3m: hist[node, cut_ptr[f] + bin, (k,) :] += (llrint(g[r(, k)] scale),
+ *  llrint(h[r(, k)] scale)) over the entries (r, bin) of every column f, node =
+ *  pos[r] - first_node in [0, num_nodes) (other rows are skipped); hist: int64,
+ *  zeroed by the caller.  Sums are formed in LDS per segment; integer sums: the
+ *  same bytes on every run.
  */
 void LaunchGbdtHistogram(const GbdtBinned& m, const float* grad, const float* hess,
-                         const int32_t* pos, int32_t first_node, uint32_t num_nodes, double scale,
-                         int64_t* hist, hipStream_t stream);
-/*! \brief bytes of 16-byte aligned scratch of LaunchGbdtBestSplits */
+                         const int32_t* pos, int32_t first_node, uint32_t num_nodes,
+                         uint32_t num_outputs, double scale, int64_t* hist, hipStream_t stream);
+/*! \brief bytes of 16-byte aligned scratch of LaunchGbdtBestSplits, in either layout */
 size_t GbdtSplitScratchBytes(uint64_t num_nodes, uint64_t num_features);
 /*!
- * \brief GB4: the best split of every node from hist (GB3) and node_sum [N x 2]
- *  (the quantised totals of the node's rows): over features with cuts, bins t
- *  and both sides for the rows without an entry, gain = 1/2 (GL^2 / (HL + l) +
- *  GR^2 / (HR + l) - G^2 / (H + l)) - gamma in f64 on sums / scale, valid with
- *  HL, HR >= min_child_weight, kept if > 0.  Equal gains: the lowest (feature,
+ * \brief GB4 / GB4m: the best split of every node from hist and node_sum (the
+ *  quantised totals of the node's rows): over features with cuts, bins t and
+ *  both sides for the rows without an entry.  Equal gains: the lowest (feature,
  *  bin), then missing-right.  feature[n] = -1 (bin 0, gain 0) without a split.
+ *  GB4: gain = 1/2 (GL^2 / (HL + l) + GR^2 / (HR + l) - G^2 / (H + l)) - gamma in
+ *  f64 on sums / scale, valid with HL, HR >= min_child_weight, kept if > 0.
+ *  GB4m: the same candidates and tie order, gain = 1/2 sum_k (GL_k^2 / (HL_k + l)
+ *  + GR_k^2 / (HR_k + l) - G_k^2 / (H_k + l)) - gamma, valid with sum_k HL_k and
+ *  sum_k HR_k >= K min_child_weight scale on the integer sums.  The float64 sum
+ *  over k has a fixed order.
  */
 void LaunchGbdtBestSplits(const int64_t* hist, const int64_t* node_sum, const int64_t* cut_ptr,
-                          uint64_t num_features, uint64_t total_bins, uint32_t num_nodes, double scale,
-                          double reg_lambda, double gamma, double min_child_weight, void* scratch,
-                          int64_t* feature, int32_t* bin, uint8_t* default_left, double* gain,
-                          hipStream_t stream);
+                          uint64_t num_features, uint64_t total_bins, uint32_t num_nodes,
+                          uint32_t num_outputs, double scale, double reg_lambda, double gamma,
+                          double min_child_weight, void* scratch, int64_t* feature, int32_t* bin,
+                          uint8_t* default_left, double* gain, hipStream_t stream);
 /*!
  * \brief GB5: pos_out[r] for every row: a row of node n = pos_in[r] -
  *  first_node in [0, num_nodes) goes to left[n] if feature[n] < 0, else by its
@@ -878,30 +887,6 @@ void LaunchGbdtAdvance(const GbdtBinned& m, const int32_t* pos_in, const int64_t
                        const int32_t* split_bin, const uint8_t* default_left, const int32_t* left,
                        const int32_t* right, int32_t first_node, uint32_t num_nodes, int32_t* pos_out,
                        hipStream_t stream);
-/*! \brief most outputs (values per leaf) of GB3m / GB4m */
-constexpr uint32_t kGbdtMaxOutputs = 32;
-/*!
- * \brief GB3m: GB3 for grad / hess [rows x num_outputs] (row-major): hist[node,
- *  cut_ptr[f] + bin, k, :] += (llrint(g[r, k] scale), llrint(h[r, k] scale));
- *  hist: int64 [num_nodes x total_bins x num_outputs x 2], zeroed by the
- *  caller.  GB3's rows, rounding and skipping rules; the same bytes on every run.
- */
-void LaunchGbdtHistogramMulti(const GbdtBinned& m, const float* grad, const float* hess,
-                              const int32_t* pos, int32_t first_node, uint32_t num_nodes,
-                              uint32_t num_outputs, double scale, int64_t* hist, hipStream_t stream);
-/*!
- * \brief GB4m: GB4 on hist [N x total_bins x K x 2] (GB3m) and node_sum [N x K x
- *  2], K = num_outputs: the same candidates and tie order, gain = 1/2 sum_k
- *  (GL_k^2 / (HL_k + l) + GR_k^2 / (HR_k + l) - G_k^2 / (H_k + l)) - gamma,
- *  valid with sum_k HL_k and sum_k HR_k >= K min_child_weight scale on the
- *  integer sums.  The float64 sum over k has a fixed order.  scratch:
- *  GbdtSplitScratchBytes(num_nodes, num_features), as for GB4.
- */
-void LaunchGbdtBestSplitsMulti(const int64_t* hist, const int64_t* node_sum, const int64_t* cut_ptr,
-                               uint64_t num_features, uint64_t total_bins, uint32_t num_nodes,
-                               uint32_t num_outputs, double scale, double reg_lambda, double gamma,
-                               double min_child_weight, void* scratch, int64_t* feature, int32_t* bin,
-                               uint8_t* default_left, double* gain, hipStream_t stream);
 // ---------------- forest inference on the row CSR (forest_kernels.hip) ----------------
 /*! \brief entries of a row GB6 stages in a wave's LDS slice (8 bytes each); a
  *  longer row is re-staged in chunks of this many at every tree level */

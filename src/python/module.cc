@@ -1317,57 +1317,30 @@ PYBIND11_MODULE(_dmlc, m) {
       },
       py::arg("columns"), py::arg("nnz"), py::arg("cut_ptr"), py::arg("cut"), py::arg("row_out"),
       py::arg("bin_out"), py::arg("error"), py::arg("stream"));
+  m.def("gbdt_max_outputs", []() { return gpu::kGbdtMaxOutputs; });
+  m.attr("gbdt_scalar") = gpu::kGbdtScalar;
   m.def(
       "gbdt_histogram",
       [stream_of, binned_of](const BinnedArg& binned, uintptr_t grad, uintptr_t hess, uintptr_t pos,
-                             int32_t first_node, uint32_t num_nodes, double scale, uintptr_t hist,
-                             uintptr_t stream) {
+                             int32_t first_node, uint32_t num_nodes, uint32_t num_outputs,
+                             double scale, uintptr_t hist, uintptr_t stream) {
         gpu::LaunchGbdtHistogram(binned_of(binned), Ptr<const float>(grad), Ptr<const float>(hess),
-                                 Ptr<const int32_t>(pos), first_node, num_nodes, scale,
+                                 Ptr<const int32_t>(pos), first_node, num_nodes, num_outputs, scale,
                                  Ptr<int64_t>(hist), stream_of(stream));
       },
       py::arg("binned"), py::arg("grad"), py::arg("hess"), py::arg("pos"), py::arg("first_node"),
-      py::arg("num_nodes"), py::arg("scale"), py::arg("hist"), py::arg("stream"));
+      py::arg("num_nodes"), py::arg("num_outputs"), py::arg("scale"), py::arg("hist"),
+      py::arg("stream"));
   m.def("gbdt_split_scratch_bytes", &gpu::GbdtSplitScratchBytes, py::arg("num_nodes"),
         py::arg("num_features"));
   m.def(
       "gbdt_best_splits",
       [stream_of](uintptr_t hist, uintptr_t node_sum, uintptr_t cut_ptr, uint64_t num_features,
-                  uint64_t total_bins, uint32_t num_nodes, double scale, double reg_lambda,
-                  double gamma, double min_child_weight, uintptr_t scratch, uintptr_t feature,
-                  uintptr_t bin, uintptr_t default_left, uintptr_t gain, uintptr_t stream) {
-        gpu::LaunchGbdtBestSplits(Ptr<const int64_t>(hist), Ptr<const int64_t>(node_sum),
-                                  Ptr<const int64_t>(cut_ptr), num_features, total_bins, num_nodes,
-                                  scale, reg_lambda, gamma, min_child_weight, Ptr<void>(scratch),
-                                  Ptr<int64_t>(feature), Ptr<int32_t>(bin),
-                                  Ptr<uint8_t>(default_left), Ptr<double>(gain), stream_of(stream));
-      },
-      py::arg("hist"), py::arg("node_sum"), py::arg("cut_ptr"), py::arg("num_features"),
-      py::arg("total_bins"), py::arg("num_nodes"), py::arg("scale"), py::arg("reg_lambda"),
-      py::arg("gamma"), py::arg("min_child_weight"), py::arg("scratch"), py::arg("feature"),
-      py::arg("bin"), py::arg("default_left"), py::arg("gain"), py::arg("stream"));
-  m.def("gbdt_max_outputs", []() { return gpu::kGbdtMaxOutputs; });
-  m.def(
-      "gbdt_histogram_multi",
-      [stream_of, binned_of](const BinnedArg& binned, uintptr_t grad, uintptr_t hess, uintptr_t pos,
-                             int32_t first_node, uint32_t num_nodes, uint32_t num_outputs,
-                             double scale, uintptr_t hist, uintptr_t stream) {
-        gpu::LaunchGbdtHistogramMulti(binned_of(binned), Ptr<const float>(grad),
-                                      Ptr<const float>(hess), Ptr<const int32_t>(pos), first_node,
-                                      num_nodes, num_outputs, scale, Ptr<int64_t>(hist),
-                                      stream_of(stream));
-      },
-      py::arg("binned"), py::arg("grad"), py::arg("hess"), py::arg("pos"), py::arg("first_node"),
-      py::arg("num_nodes"), py::arg("num_outputs"), py::arg("scale"), py::arg("hist"),
-      py::arg("stream"));
-  m.def(
-      "gbdt_best_splits_multi",
-      [stream_of](uintptr_t hist, uintptr_t node_sum, uintptr_t cut_ptr, uint64_t num_features,
                   uint64_t total_bins, uint32_t num_nodes, uint32_t num_outputs, double scale,
                   double reg_lambda, double gamma, double min_child_weight, uintptr_t scratch,
                   uintptr_t feature, uintptr_t bin, uintptr_t default_left, uintptr_t gain,
                   uintptr_t stream) {
-        gpu::LaunchGbdtBestSplitsMulti(
+        gpu::LaunchGbdtBestSplits(
             Ptr<const int64_t>(hist), Ptr<const int64_t>(node_sum), Ptr<const int64_t>(cut_ptr),
             num_features, total_bins, num_nodes, num_outputs, scale, reg_lambda, gamma,
             min_child_weight, Ptr<void>(scratch), Ptr<int64_t>(feature), Ptr<int32_t>(bin),

@@ -140,6 +140,69 @@ def test_best_splits_against_the_float64_table(K, num_nodes, mcw):
             assert torch.equal(got[k], scalar[k]), k
 
 
+@pytest.mark.parametrize("mcw", [1.0, 20.0])
+@pytest.mark.parametrize("num_nodes", [1, 33])
+def test_one_output_equals_the_scalar_ops_bit_for_bit(num_nodes, mcw):
+    """K = 1 given as [rows, 1] runs GB3m / GB4m<1>, [rows] runs GB3 / GB4: the same histogram
+    bytes, the same candidates in the same order and the same float64 gain expression."""
+    g, h, pos, scale, hist, sums = _case(1, num_nodes)
+    cut_ptr = _binned()[0]["cut_ptr"]
+    # on the CPU first: scale is a power of two, so GB4's validity rule (float64 sums / scale
+    # against mcw) and GB4m's (integer sums against K mcw scale) are one rule on this input
+    assert math.frexp(scale)[0] == 0.5
+    scalar_table = ref.gain_table(hist[:, :, 0], sums[:, 0], cut_ptr, scale, 1.0, 0.0, mcw)
+    assert np.array_equal(scalar_table, _gain_table(hist, sums, cut_ptr, scale, 1.0, 0.0, mcw)[0])
+    binned = _binned()[1]
+    g, h, pos = (torch.from_numpy(a).cuda() for a in (g, h, pos))
+    multi = ops.grad_histogram_multi(binned, g, h, pos, num_nodes, scale, FIRST)
+    scalar = ops.grad_histogram(binned, g[:, 0].contiguous(), h[:, 0].contiguous(), pos,
+                                num_nodes, scale, FIRST)
+    assert tuple(multi.shape) == (num_nodes, int(cut_ptr[-1]), 1, 2)
+    assert torch.equal(multi.squeeze(2), scalar)
+    assert torch.equal(scalar.cpu(), torch.from_numpy(hist[:, :, 0]))
+    node_sum, cuts = torch.from_numpy(sums).cuda(), binned["cut_ptr"]
+    got = ops.best_splits_multi(multi, node_sum, cuts, scale, 1.0, 0.0, mcw)
+    want = ops.best_splits(scalar, node_sum[:, 0].contiguous(), cuts, scale, 1.0, 0.0, mcw)
+    assert (want["feature"] >= 0).all()
+    for k in ("feature", "bin", "default_left"):
+        assert torch.equal(got[k], want[k]), k
+    assert torch.equal(got["gain"].view(torch.int64), want["gain"].view(torch.int64))
+
+
+def _wrong_call(name, what):
+    """a call of ops.<name> whose hist / grad has the wrong dtype or the other layout's rank"""
+    vector = name.endswith("_multi")
+    if what == "rank":
+        vector = not vector
+    if name.startswith("grad_histogram"):
+        g = torch.zeros((ROWS, 1) if vector else (ROWS,), device="cuda",
+                        dtype=torch.float64 if what == "dtype" else torch.float32)
+        pos = torch.zeros(ROWS, dtype=torch.int32, device="cuda")
+        return lambda: getattr(ops, name)(_binned()[1], g, g, pos, 1, 1.0)
+    cut_ptr = _binned()[1]["cut_ptr"]
+    middle = (1,) if vector else ()
+    hist = torch.zeros((2, int(cut_ptr[-1])) + middle + (2,), device="cuda",
+                       dtype=torch.int32 if what == "dtype" else torch.int64)
+    node_sum = torch.ones((2,) + middle + (2,), dtype=torch.int64, device="cuda")
+    return lambda: getattr(ops, name)(hist, node_sum, cut_ptr, 1.0)
+
+
+@pytest.mark.parametrize("name", ["grad_histogram", "grad_histogram_multi", "best_splits",
+                                  "best_splits_multi"])
+def test_a_wrong_dtype_is_refused_under_the_functions_own_name(name):
+    with pytest.raises(ValueError) as err:
+        _wrong_call(name, "dtype")()
+    assert str(err.value).startswith(name + ": "), str(err.value)
+
+
+@pytest.mark.parametrize("name", ["best_splits", "best_splits_multi", "grad_histogram"])
+def test_the_other_layouts_rank_is_refused(name):
+    """best_splits takes no 4-D hist, best_splits_multi no 3-D one, grad_histogram no [rows, 1]"""
+    with pytest.raises(ValueError) as err:
+        _wrong_call(name, "rank")()
+    assert str(err.value).startswith(name + ": "), str(err.value)
+
+
 @functools.lru_cache(maxsize=None)
 def _three_classes(rows=600):
     """class c has feature c; features 3 .. 9 are noise"""
