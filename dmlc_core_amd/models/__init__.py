@@ -450,9 +450,10 @@ class SparseGBDT:
     ``h = max(2 p (1 - p), 1e-16)``, the loss is the mean cross entropy.
     ``"squared"`` / ``"logistic"``: labels are ``[rows, K]`` (multi-target,
     multi-label) and the scalar formulas apply per output; row weights
-    multiply every output.  Rank objectives have one output.  Out of scope: a
-    fused forest walk that sums vector margins (``method="rows"`` gathers the
-    vector leaves of GB6's leaf ids in torch), and one-tree-per-class boosting."""
+    multiply every output.  Rank objectives have one output.
+    ``predict(method="rows")`` is one fused launch for these trees too (GB6m:
+    the forest walk sums the vector leaves to ``[rows, K]`` margins).  Out of
+    scope: one-tree-per-class boosting."""
 
     _RANK_WEIGHTING = {"rank:ndcg": "ndcg", "rank:pairwise": "none"}
 
@@ -663,20 +664,8 @@ class SparseGBDT:
         """the trees packed for GB6, repacked when their number has changed (and only then: a
         tree replaced in place, or new ``cuts``, needs ``self._packed = None``)"""
         if self._packed is None or self._packed["trees"] != len(self.trees):
-            trees = self.trees
-            if self.num_outputs > 1:  # GB6 walks to leaf ids only: a zero stands in for the vector
-                trees = [dict(t, leaf=torch.zeros_like(t["leaf"][:, 0])) for t in trees]
-            self._packed = ops.pack_forest(trees, self.cuts)
+            self._packed = ops.pack_forest(self.trees, self.cuts)
         return self._packed
-
-    def _gather_leaves(self, ids) -> torch.Tensor:
-        """the margins ``[rows, K]`` of vector-leaf trees from the nodes ``ids [rows, T]`` the
-        rows end on, summed in f32 in tree order (the order of the level-by-level path)"""
-        margin = torch.zeros((ids.shape[0], self.num_outputs), dtype=torch.float32,
-                             device=ids.device)
-        for t, tree in enumerate(self.trees):
-            margin = margin + tree["leaf"][ids[:, t].long()]
-        return margin
 
     def predict(self, csr, method: str = "levels") -> torch.Tensor:
         """The margins of the rows of ``csr`` (logits under ``"logistic"`` and
@@ -694,8 +683,6 @@ class SparseGBDT:
         if self.cuts is None:
             raise ValueError("SparseGBDT.predict: the model has no cuts (fit or boost first)")
         if method == "rows":
-            if self.num_outputs > 1:
-                return self._gather_leaves(ops.predict_forest(csr, self._forest(), "leaf"))
             return ops.predict_forest(csr, self._forest(), "margin")
         binned = ops.bin_features(csr, self.cuts, self.num_features)
         rows, dev = int(binned["rows"]), binned["row"].device

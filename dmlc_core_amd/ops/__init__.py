@@ -11,7 +11,8 @@ Histogram gradient-boosted trees run on the column-major binned matrix:
 Trees with K values per leaf (multiclass, multi-target) take the K-channel
 :func:`grad_histogram_multi` -> :func:`best_splits_multi` instead.
 The trained forest scores row-major batches in one launch:
-:func:`pack_forest` once, then :func:`predict_forest` for margins or leaf ids.
+:func:`pack_forest` once, then :func:`predict_forest` for margins or leaf ids
+(GB6; GB6m sums vector leaves to ``[rows, K]`` margins in the same launch).
 Ranking on query groups: :func:`qid_groups`, then :func:`rank_loss` / :func:`ndcg`
 for a differentiable model, or :func:`rank_grad_hess` for the per-row gradients
 and hessians of a boosting round (LambdaMART).
@@ -1776,7 +1777,15 @@ def pack_forest(trees, cuts: Dict) -> Dict:
     device-to-host read (the checks).  Raises ``ValueError`` for trees of
     unequal size, a size that is not ``2**k - 1`` with depth ``k - 1`` in
     [1, 14], a split on a feature without cuts, or a ``bin`` outside its
-    feature's cuts.  No trees give ``T = 0``."""
+    feature's cuts.  No trees give ``T = 0``.
+
+    Vector leaves (``SparseGBDT(num_outputs=K)``): when the trees' ``leaf`` is
+    2-D float32 ``[size, K]``, the dict has two more keys, ``"leaf_value"``:
+    float32 ``[T, size, K]``, contiguous (the stacked ``leaf``), and
+    ``"outputs": K``; word 1 of a leaf node is then 0.  All trees have the same
+    K in [1, ``_dmlc.gbdt_max_outputs()``]; 1-D among 2-D leaves, unequal K or
+    a K out of range raise ``ValueError`` before any device read.  A forest of
+    1-D leaves has neither key."""
     cut_ptr, cut = cuts.get("cut_ptr"), cuts.get("cut")
     nfeat = cut_ptr.numel() - 1 if isinstance(cut_ptr, torch.Tensor) else -1
     dev = cut.device if isinstance(cut, torch.Tensor) else None
@@ -1786,21 +1795,36 @@ def pack_forest(trees, cuts: Dict) -> Dict:
         return {"node": torch.empty((0, 0, 2), dtype=torch.int32, device=dev), "trees": 0,
                 "size": 0, "depth": 0}
     size = int(trees[0]["feature"].numel())
+    first_leaf = trees[0].get("leaf")
+    vector = isinstance(first_leaf, torch.Tensor) and first_leaf.dim() == 2
+    outputs = int(first_leaf.shape[1]) if vector else 0
+    kmax = int(_dmlc.gbdt_max_outputs())
+    if vector and not 1 <= outputs <= kmax:
+        raise ValueError(f"pack_forest: vector leaves hold 1 .. {kmax} values, got {outputs}")
     for tree in trees:
         for k, dt in (("feature", torch.int64), ("bin", torch.int32), ("default_left", torch.bool),
                       ("leaf", torch.float32)):
             t = tree.get(k)
-            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1 or t.device != dev:
-                raise ValueError(f"pack_forest: a tree's {k!r} must be a 1-D {dt} tensor on {dev}")
-            if t.numel() != size:
-                raise ValueError(f"pack_forest: trees of unequal size ({t.numel()} and {size} "
+            dims = 2 if vector and k == "leaf" else 1
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != dims \
+                    or t.device != dev:
+                raise ValueError(f"pack_forest: a tree's {k!r} must be a {dims}-D {dt} tensor on "
+                                 f"{dev}" + (" (as the first tree's)" if dims == 2 else ""))
+            if t.shape[0] != size:
+                raise ValueError(f"pack_forest: trees of unequal size ({t.shape[0]} and {size} "
                                  "nodes)")
+            if dims == 2 and t.shape[1] != outputs:
+                raise ValueError(f"pack_forest: vector leaves of unequal width ({t.shape[1]} and "
+                                 f"{outputs} values)")
     depth = (size + 1).bit_length() - 2
     if size != 2 ** (depth + 1) - 1 or not 1 <= depth <= 14:
         raise ValueError(f"pack_forest: a tree has {size} nodes, not 2**(depth + 1) - 1 with depth "
                          "in [1, 14]")
     feature, tbin, left, leaf = (torch.stack([t[k] for t in trees])
                                  for k in ("feature", "bin", "default_left", "leaf"))
+    leaf_value = leaf.contiguous() if vector else None  # [T, size, K]
+    if vector:
+        leaf = torch.zeros(leaf.shape[:2], dtype=torch.float32, device=dev)  # word 1 of a leaf: 0
     inner = feature >= 0
     inner[:, size // 2:] = False  # the last level has no children
     known = inner & (feature < nfeat)
@@ -1825,7 +1849,10 @@ def pack_forest(trees, cuts: Dict) -> Dict:
     word0 = torch.where(inner, torch.where(left, f - (1 << 31), f), torch.full_like(f, -1))
     word1 = torch.where(inner, thr, leaf).view(torch.int32)
     node = torch.stack([word0.to(torch.int32), word1], 2).contiguous()
-    return {"node": node, "trees": len(trees), "size": size, "depth": depth}
+    forest = {"node": node, "trees": len(trees), "size": size, "depth": depth}
+    if vector:
+        forest.update(leaf_value=leaf_value, outputs=outputs)
+    return forest
 
 
 def predict_forest(csr: Dict, forest: Dict, output: str = "margin",
@@ -1836,6 +1863,15 @@ def predict_forest(csr: Dict, forest: Dict, output: str = "margin",
     leaf_0) + leaf_1) + ...`` in f32 in tree order -- the bytes of
     ``SparseGBDT.predict``'s level-by-level path.  ``output="leaf"``: int32
     ``[rows, T]``, the heap id of the node each row ends on in each tree.
+
+    A forest of vector leaves (:func:`pack_forest` of 2-D ``leaf``, keys
+    ``"leaf_value"`` float32 ``[T, size, K]`` and ``"outputs": K``) runs GB6m:
+    the same walk in the same launch, ``output="margin"`` is float32 ``[rows,
+    K]``, ``margin[r, k] = ((0 + leaf_value[0, i_0, k]) + leaf_value[1, i_1,
+    k]) + ...`` in tree order for every k, ``i_t`` the node the row ends on in
+    tree t -- again the bytes of the level-by-level path; ``"leaf"`` is
+    unchanged.  ``leaf_value`` is checked before a launch (dtype, shape,
+    contiguity, device, K against ``outputs``); no rows give zeros ``[0, K]``.
 
     At a node an entry of the split feature goes left when ``value <=
     threshold``; a row without one takes the node's default side; ids that no
@@ -1864,15 +1900,27 @@ def predict_forest(csr: Dict, forest: Dict, output: str = "margin",
     ntrees, size, depth = int(node.shape[0]), int(node.shape[1]), int(forest.get("depth", 0))
     if ntrees > 0 and (not 1 <= depth <= 14 or size != 2 ** (depth + 1) - 1):
         raise ValueError("predict_forest: forest['depth'] does not fit the node tensor")
+    table, outputs = forest.get("leaf_value"), forest.get("outputs", _dmlc.gbdt_scalar)
+    if table is not None or outputs != _dmlc.gbdt_scalar:
+        if isinstance(outputs, bool) or not isinstance(outputs, int) \
+                or not 1 <= outputs <= int(_dmlc.gbdt_max_outputs()):
+            raise ValueError("predict_forest: forest['outputs'] must be an int in "
+                             f"[1, {int(_dmlc.gbdt_max_outputs())}], got {outputs!r}")
+        if not isinstance(table, torch.Tensor) or table.dtype != torch.float32 \
+                or tuple(table.shape) != (ntrees, size, outputs) or not table.is_contiguous():
+            raise ValueError("predict_forest: forest['leaf_value'] must be a contiguous float32 "
+                             f"[{ntrees}, {size}, {outputs}] tensor (pack_forest's)")
     csr = _unpair(csr)
     view, rows = _view(csr)
     _check_device("forest['node']", node, csr)
+    _check_device("forest['leaf_value']", table, csr)
     if csr.get("value") is not None and csr["value"].numel() != csr["index"].numel():
         raise ValueError(f"csr['value'] has {csr['value'].numel()} entries, "
                          f"csr['index'] {csr['index'].numel()}")
     dev = node.device
     if output == "margin":
-        out = torch.zeros(rows, dtype=torch.float32, device=dev)
+        many = (outputs,) if table is not None else ()
+        out = torch.zeros((rows,) + many, dtype=torch.float32, device=dev)
     else:
         out = torch.zeros((rows, ntrees), dtype=torch.int32, device=dev)
     if rows == 0 or ntrees == 0:
@@ -1880,7 +1928,8 @@ def predict_forest(csr: Dict, forest: Dict, output: str = "margin",
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     _dmlc.forest_predict(view, _ptr(node), ntrees, size, depth,
                          _ptr(out) if output == "margin" else 0,
-                         _ptr(out) if output == "leaf" else 0, _ptr(err), _stream())
+                         _ptr(out) if output == "leaf" else 0, _ptr(err), _stream(),
+                         _ptr(table), outputs)
     if validate and int(err.item()):
         raise ValueError("predict_forest: a value is NaN")
     return out

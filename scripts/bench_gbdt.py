@@ -30,6 +30,10 @@ cuts for each of 1 M features 64 nodes would need 262 GB.
              cached) and ops.pack_forest alone.  The two margin vectors must be
              equal bit for bit.  `rows_share`: the time one pass over the CSR's
              bytes takes at the measured device copy rate, over the measured time
+             --vector-leaves K[,K..]: the same trees with random [size, K] leaves in
+             a softmax model (a K-output histogram of 1 M features does not fit):
+             method="rows" (GB6m, one launch) against what it replaced, GB6's leaf
+             ids and a torch gather and add per tree; the margins must be equal
 
   --outputs K  instead of the sections after `one-time`: ops.grad_histogram_multi
              and ops.best_splits_multi (GB3m / GB4m, K gradients per row) at each
@@ -65,6 +69,7 @@ def main():
     ap.add_argument("--nodes", default="1,8,64")
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--skip-torch", action="store_true")
+    ap.add_argument("--vector-leaves", default="", help="the predict section: these K too")
     ap.add_argument("--outputs", type=int, default=0,
                     help="K > 0: only the one-time section and the K-output ops")
     args = ap.parse_args()
@@ -89,6 +94,20 @@ def main():
         ms.sort()
         return {"ms": round(ms[len(ms) // 2], 3), "ms_min": round(ms[0], 3),
                 "ms_max": round(ms[-1], 3)}
+
+    def timed_pair(a, b):
+        """`timed` for two ways to the same result, their windows alternating"""
+        a(), b()
+        torch.cuda.synchronize()
+        ms = ([], [])
+        for _ in range(args.iters):
+            for fn, out in zip((a, b), ms):
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                out.append((time.perf_counter() - t0) * 1e3)
+        return [{"ms": round(sorted(m)[len(m) // 2], 3), "ms_min": round(min(m), 3),
+                 "ms_max": round(max(m), 3)} for m in ms]
 
     def note(name, r):
         res[name] = r
@@ -170,20 +189,6 @@ def main():
                           2).long()
         cols = [(gk[:, k].contiguous(), hk[:, k].contiguous()) for k in range(K)]  # not timed
         cut_ptr = binned["cut_ptr"]
-
-        def timed_pair(a, b):
-            """`timed` for two ways to the same result, their windows alternating"""
-            a(), b()
-            torch.cuda.synchronize()
-            ms = ([], [])
-            for _ in range(args.iters):
-                for fn, out in zip((a, b), ms):
-                    t0 = time.perf_counter()
-                    fn()
-                    torch.cuda.synchronize()
-                    out.append((time.perf_counter() - t0) * 1e3)
-            return [{"ms": round(sorted(m)[len(m) // 2], 3), "ms_min": round(min(m), 3),
-                     "ms_max": round(max(m), 3)} for m in ms]
 
         for n in (int(s) for s in args.nodes.split(",")):
             pos = torch.randint(0, n, (rows,), device=dev, generator=gen, dtype=torch.int32)
@@ -356,6 +361,25 @@ def main():
     res["predict_trees_with_splits"] = sum(int(t["feature"][0]) >= 0 for t in model.trees)
     assert torch.equal(model.predict(csr, method="rows"), model.predict(csr)), \
         "predict: the rows path and the levels path differ"
+    for K in (int(s) for s in args.vector_leaves.split(",") if s):
+        multi = SparseGBDT(feats, max_bins=args.max_bins, max_depth=6, objective="softmax",
+                           num_outputs=K)
+        multi.cuts = model.cuts
+        multi.trees = [dict(t, leaf=torch.randn((t["leaf"].numel(), K), device=dev, generator=gen))
+                       for t in model.trees]
+
+        def gathered():  # method="rows" before GB6m; model's forest: the same nodes, cached
+            ids = ops.predict_forest(csr, model._forest(), "leaf")
+            margin = torch.zeros((rows, K), dtype=torch.float32, device=dev)
+            for t, tree in enumerate(multi.trees):
+                margin = margin + tree["leaf"][ids[:, t].long()]
+            return margin
+        r, r1 = timed_pair(lambda: multi.predict(csr, method="rows"), gathered)
+        note(f"predict_rows_8_K{K}", r)
+        note(f"predict_leaf_ids_torch_gather_8_K{K}", r1)
+        res[f"gather_over_rows_K{K}"] = ratio(r1, r)
+        assert torch.equal(multi.predict(csr, method="rows"), gathered()), \
+            "predict: GB6m and the gathered leaves differ"
     print(json.dumps(res), flush=True)
 
 

@@ -1,12 +1,14 @@
 /*!
  * \file src/gpu/forest_kernels.hip
- * \brief GB6: fused inference of a packed forest on the row-major CSR -- every
- *  tree, every level, the margin sum or the leaf ids in one launch, without a
- *  transpose and without bins.
+ * \brief GB6 / GB6m: fused inference of a packed forest on the row-major CSR --
+ *  every tree, every level, the margin sum or the leaf ids in one launch,
+ *  without a transpose and without bins.
  *
  *  GB6 k_forest_predict  one wave per row, one lane per tree, 64 trees per
  *                        pass, all 64 walking level-synchronously over the
  *                        row's (id, value) pairs staged in the wave's LDS slice.
+ *  GB6m the same, <.., kVector>: leaves of K values, margins [rows, K]; after a
+ *                        pass the lanes regroup as (tree, output) to sum.
  *
  *  The forest (ops.pack_forest) is int32 [T, size, 2] in heap layout, 8 bytes a
  *  node: word 0 = feature | default_left << 31 (-1: a leaf), word 1 = the bits
@@ -46,6 +48,29 @@
  *  leaf_1) + ..., the order of the level-by-level path.  No atomics, one owner
  *  per row: the same inputs give the same bytes.  Leaf ids are written by the
  *  lanes at leaf[r, pass * 64 + lane].
+ *
+ *  GB6m: vector leaves (ForestView::outputs = K in 1 .. kGbdtMaxOutputs).  The
+ *  same kernel with kVector set: the walk above is shared line for line, word 1
+ *  of a leaf is unused, and the leaves' K values lie in a f32 table leaf_value
+ *  [T, size, K].  margin[r, k] = ((0 + leaf_value[0, i_0, k]) + leaf_value[1,
+ *  i_1, k]) + ... for every k, the level-by-level path's order again.  After a
+ *  pass lane l holds the end node i_l of tree t0 + l, and the wave turns from
+ *  one lane per tree to one lane per (tree, output): with Kp = the power of two
+ *  >= K and G = 64 / Kp, lane = g * Kp + k.  A step takes G consecutive trees:
+ *  lane (g, k) fetches the end node of tree u = step * G + g from lane u (one
+ *  ds_bpermute) and loads leaf_value[((t0 + u) * size + i_u) * K + k] -- a
+ *  tree's K floats are one segment, one wave instruction reads G segments --
+ *  and then the G values of output k are added in tree order, acc += the value
+ *  of lane g' * Kp + k for g' = 0 .. G - 1 (a bpermute each), so every lane of
+ *  one k carries the same accumulator across steps and passes.  Trees past the
+ *  pass's last and lanes with k >= K form no address and add nothing.  The
+ *  loads of kVecSteps successive steps are issued before the first ordered add
+ *  of the block: the adds are a dependent chain, the loads are not.  Per pass:
+ *  ceil(here / G) loads and bpermutes and `here` bpermute + add pairs, where
+ *  the scalar kernel has `here` readlane + add pairs.  Lanes 0 .. K - 1 store
+ *  the row's K margins as one segment.  Kp is a runtime shift (no template per
+ *  Kp: the sum is a small part of a row's time, and the flag already doubles
+ *  the file's instantiations from four to eight); no LDS beyond the row slice.
  */
 #include <dmlc/gpu/hip_utils.h>
 #include <dmlc/logging.h>
@@ -68,6 +93,8 @@ constexpr uint32_t kNoFeature = 0xFFFFFFFFu;
  *  step of the scan: its LDS reads issue together and it has no tail */
 constexpr uint32_t kStep = 16;
 static_assert(kCap % kStep == 0, "a full slice needs no padding");
+/*! \brief GB6m: steps of the vector sum whose leaf loads are in flight before the ordered adds */
+constexpr uint32_t kVecSteps = 4;
 static_assert(kForestTreesPerPass == dev::kWave, "one lane per tree of a pass");
 
 /*! \brief one thread ORs the wave's error into the status word (not an output) */
@@ -131,11 +158,57 @@ __device__ __forceinline__ void scan(const uint2* s_row, uint32_t count, uint32_
   *x = v;
 }
 
-template <typename IndexType, bool kHasValue>
+/*! \brief GB6m: the leaf table and how the wave's lanes regroup to sum it: lane = g * Kp + k,
+ *  Kp = 1 << kp_log >= outputs; unused by GB6 */
+struct LeafTable {
+  const float* __restrict__ value;  // [trees x size x outputs]
+  uint32_t outputs, kp_log;
+};
+
+/*!
+ * \brief GB6m's sum of one pass: acc += leaf_value[t0 + u, i_u, k] for u = 0 .. here - 1 in
+ *  that order, i_u = lane u's `i`; acc is the same in every lane of one k (k = lane % Kp < K).
+ *  Called by the whole wave; i < size and t0 + u < trees, so every address is in the table.
+ */
+__device__ __forceinline__ float add_leaf_vectors(const LeafTable& table, uint32_t t0,
+                                                  uint32_t here, uint32_t size, uint32_t i,
+                                                  float acc) {
+  const uint32_t lane = dev::lane_id();
+  const uint32_t k = lane & ((1u << table.kp_log) - 1u), g = lane >> table.kp_log;
+  const uint32_t group = static_cast<uint32_t>(dev::kWave) >> table.kp_log;  // G trees a step
+  const bool mine = k < table.outputs;
+  for (uint32_t u0 = 0; u0 < here; u0 += kVecSteps * group) {
+    float v[kVecSteps];
+#pragma unroll
+    for (uint32_t j = 0; j < kVecSteps; ++j) {  // independent loads, all issued before the adds
+      const uint32_t u = u0 + j * group + g;    // a lane index once it is < here <= 64
+      v[j] = 0.0f;
+      if (u0 + j * group >= here) continue;  // wave-uniform: no tree left for this step
+      const uint32_t id = static_cast<uint32_t>(
+          __shfl(static_cast<int>(i), static_cast<int>(u & (dev::kWave - 1)), dev::kWave));
+      if (mine && u < here) {
+        v[j] = table.value[(static_cast<size_t>(t0 + u) * size + id) * table.outputs + k];
+      }
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < kVecSteps; ++j) {
+      const uint32_t first = u0 + j * group;  // wave-uniform, as is the trip count below
+      const uint32_t count = first < here ? (here - first < group ? here - first : group) : 0;
+      for (uint32_t gg = 0; gg < count; ++gg) {
+        const float x = __shfl(v[j], static_cast<int>((gg << table.kp_log) + k), dev::kWave);
+        if (mine) acc += x;
+      }
+    }
+  }
+  return acc;
+}
+
+template <typename IndexType, bool kHasValue, bool kVector>
 __global__ __launch_bounds__(kThreads) void k_forest_predict(
     const uint64_t* __restrict__ offset, const RowEntries<IndexType, kHasValue> src, size_t nrows,
     const int2* __restrict__ node, uint32_t trees, uint32_t size, uint32_t depth,
-    float* __restrict__ margin, int32_t* __restrict__ leaf, uint32_t* error) {
+    const LeafTable table, float* __restrict__ margin, int32_t* __restrict__ leaf,
+    uint32_t* error) {
   __shared__ __attribute__((aligned(16))) uint2 s_lds[kWaves][kCap];
   const uint32_t lane = dev::lane_id();
   const uint32_t wave = threadIdx.x / dev::kWave;
@@ -185,12 +258,20 @@ __global__ __launch_bounds__(kThreads) void k_forest_predict(
       if (leaf != nullptr && live) leaf[r * trees + t] = static_cast<int32_t>(i);
       if (margin != nullptr) {
         const uint32_t here = trees - t0 < dev::kWave ? trees - t0 : dev::kWave;
-        for (uint32_t l = 0; l < here; ++l) {
-          acc += __int_as_float(__builtin_amdgcn_readlane(nd.y, static_cast<int>(l)));
+        if (kVector) {
+          acc = add_leaf_vectors(table, t0, here, size, i, acc);
+        } else {
+          for (uint32_t l = 0; l < here; ++l) {
+            acc += __int_as_float(__builtin_amdgcn_readlane(nd.y, static_cast<int>(l)));
+          }
         }
       }
     }
-    if (margin != nullptr && lane == 0) margin[r] = acc;
+    if (kVector) {  // lanes 0 .. K - 1 are (g = 0, k = lane): one segment a row
+      if (margin != nullptr && lane < table.outputs) margin[r * table.outputs + lane] = acc;
+    } else if (margin != nullptr && lane == 0) {
+      margin[r] = acc;
+    }
   }
   report(bad, kGbdtErrNaN, error);
 }
@@ -203,19 +284,37 @@ void LaunchForestPredict(const CsrView& csr, const ForestView& forest, float* ma
       << "forest predict: size must be 2^(depth + 1) - 1 with depth in [1, 14]";
   CHECK(margin != nullptr || leaf != nullptr) << "forest predict: no output";
   CHECK(error != nullptr) << "forest predict: no error word";
+  const bool vector = forest.outputs != kGbdtScalar;
+  if (vector) {
+    CHECK(forest.outputs <= kGbdtMaxOutputs)
+        << "forest predict: " << forest.outputs << " outputs, at most " << kGbdtMaxOutputs;
+    CHECK(margin == nullptr || forest.leaf_value != nullptr || forest.trees == 0)
+        << "forest predict: margins of vector leaves need leaf_value";
+    CHECK_EQ((reinterpret_cast<uintptr_t>(forest.leaf_value) |
+              reinterpret_cast<uintptr_t>(margin)) & 3u, 0u)
+        << "forest predict: leaf_value / margin not 4-byte aligned";
+  }
   if (csr.nrows == 0 || forest.trees == 0) return;
   CHECK(forest.node != nullptr) << "forest predict: no nodes";
   CHECK_EQ(reinterpret_cast<uintptr_t>(forest.node) & 7u, 0u)
       << "forest predict: nodes not 8-byte aligned";
+  LeafTable table{forest.leaf_value, forest.outputs, 0};
+  while (vector && (1u << table.kp_log) < forest.outputs) ++table.kp_log;
   const dim3 grid(GridFor(csr.nrows, kWaves));
   DispatchIndexValue(csr, [&](auto tag, auto has_value) {
     using IndexType = decltype(tag);
     constexpr bool kHasValue = decltype(has_value)::value;
-    hipLaunchKernelGGL((k_forest_predict<IndexType, kHasValue>), grid, dim3(kThreads), 0, stream,
-                       csr.offset,
-                       RowEntries<IndexType, kHasValue>{IndexOf<IndexType>(csr), csr.value},
-                       csr.nrows, reinterpret_cast<const int2*>(forest.node), forest.trees,
-                       forest.size, forest.depth, margin, leaf, error);
+    const RowEntries<IndexType, kHasValue> src{IndexOf<IndexType>(csr), csr.value};
+    const auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, grid, dim3(kThreads), 0, stream, csr.offset, src, csr.nrows,
+                         reinterpret_cast<const int2*>(forest.node), forest.trees, forest.size,
+                         forest.depth, table, margin, leaf, error);
+    };
+    if (vector) {
+      launch(k_forest_predict<IndexType, kHasValue, true>);
+    } else {
+      launch(k_forest_predict<IndexType, kHasValue, false>);
+    }
   });
   DMLC_HIP_CHECK_LAUNCH();
 }

@@ -45,8 +45,8 @@
  *   GB3 / GB3m grad histogram LaunchGbdtHistogram (gbdt_kernels.hip)
  *   GB4 / GB4m best splits    LaunchGbdtBestSplits (gbdt_kernels.hip)
  *   GB5 advance rows     LaunchGbdtAdvance        (gbdt_kernels.hip)
- *   GB6 forest inference LaunchForestPredict      (forest_kernels.hip)
- * The launchers of K9, K11, M1 / M2, FF1 / FF2, G2, GB6 and the transpose take
+ *   GB6 / GB6m forest inference LaunchForestPredict (forest_kernels.hip)
+ * The launchers of K9, K11, M1 / M2, FF1 / FF2, G2, GB6 / GB6m and the transpose take
  * their CSR operand as one CsrView and pick the kernel for its index width
  * (and pair layout) themselves; launch_common.h holds what they share.
  * All launchers are asynchronous on `stream` and never allocate or
@@ -898,10 +898,15 @@ constexpr uint32_t kForestTreesPerPass = 64;
  *  of i: 2i + 1, 2i + 2), size = 2^(depth + 1) - 1, depth 1 .. 14.  Word 0 of a
  *  node: feature (< 2^28) | default_left << 31, or -1 for a leaf; word 1: the
  *  bits of the float threshold (go left when x <= it) or of the leaf value.
+ *  outputs = kGbdtScalar: that layout, leaf_value unused.  outputs = K in 1 ..
+ *  kGbdtMaxOutputs: vector leaves -- word 1 of a leaf is unused, and the
+ *  leaves' values are leaf_value f32 [trees x size x K], a leaf's K contiguous.
  */
 struct ForestView {
   const int32_t* node;  // 8-byte aligned
   uint32_t trees, size, depth;
+  const float* leaf_value;  // 4-byte aligned
+  uint32_t outputs;
 };
 /*!
  * \brief GB6: walk every row of `csr` (the CSR shapes of K11: value may be
@@ -914,6 +919,10 @@ struct ForestView {
  *  split feature are ignored.  A NaN value ORs kGbdtErrNaN into *error (a device
  *  word the caller zeroed) and goes right.  No atomics on the outputs; nrows ==
  *  0 or trees == 0 returns before any HIP call.
+ *  GB6m (forest.outputs = K >= 1): the same walk and the same leaf ids; margin
+ *  is [nrows x K], margin[r, k] = ((0 + leaf_value[0, i_0, k]) + leaf_value[1,
+ *  i_1, k]) + ... in f32 in tree order, i_t the node the row ends on in tree t.
+ *  K <= kGbdtMaxOutputs, and leaf_value is needed when margin is asked for.
  */
 void LaunchForestPredict(const CsrView& csr, const ForestView& forest, float* margin, int32_t* leaf,
                          uint32_t* error, hipStream_t stream);

@@ -1369,14 +1369,18 @@ PYBIND11_MODULE(_dmlc, m) {
   m.def(
       "forest_predict",
       [stream_of](const CsrArg& csr, uintptr_t node, uint32_t trees, uint32_t size, uint32_t depth,
-                  uintptr_t margin, uintptr_t leaf, uintptr_t error, uintptr_t stream) {
+                  uintptr_t margin, uintptr_t leaf, uintptr_t error, uintptr_t stream,
+                  uintptr_t leaf_value, uint32_t outputs) {
         gpu::LaunchForestPredict(View(csr),
-                                 gpu::ForestView{Ptr<const int32_t>(node), trees, size, depth},
+                                 gpu::ForestView{Ptr<const int32_t>(node), trees, size, depth,
+                                                 Ptr<const float>(leaf_value), outputs},
                                  Ptr<float>(margin), Ptr<int32_t>(leaf), Ptr<uint32_t>(error),
                                  stream_of(stream));
       },
       py::arg("csr"), py::arg("node"), py::arg("trees"), py::arg("size"), py::arg("depth"),
-      py::arg("margin"), py::arg("leaf"), py::arg("error"), py::arg("stream"));
+      py::arg("margin"), py::arg("leaf"), py::arg("error"), py::arg("stream"),
+      py::arg("leaf_value") = uintptr_t{0}, py::arg("outputs") = gpu::kGbdtScalar,
+      "GB6; outputs = K >= 1 with leaf_value f32 [trees, size, K]: GB6m, margin [rows, K]");
   m.def("forest_staged_row_entries", []() { return gpu::kForestRowEntries; },
         "entries of a row GB6 stages in LDS; a longer row is re-staged in chunks per level");
   m.def("forest_trees_per_pass", []() { return gpu::kForestTreesPerPass; },
