@@ -453,14 +453,27 @@ class SparseGBDT:
     multiply every output.  Rank objectives have one output.
     ``predict(method="rows")`` is one fused launch for these trees too (GB6m:
     the forest walk sums the vector leaves to ``[rows, K]`` margins).  Out of
-    scope: one-tree-per-class boosting."""
+    scope: one-tree-per-class boosting.
+
+    Weighted cuts (``cut_weight="row"``): :meth:`fit` passes ``csr["weight"]``
+    to :func:`~dmlc_core_amd.ops.feature_cuts`, so the bins of a feature lie
+    where the weight of its rows is (the weighted quantile rule, GB1w), not
+    where the rows are -- for a down-sampled class, an importance-weighted log
+    or de-duplicated rows with their counts as weights.  It needs a ``weight``
+    in the CSR and is refused for the rank objectives, which take no row
+    weights.  The default ``"none"`` places the cuts by counting entries."""
 
     _RANK_WEIGHTING = {"rank:ndcg": "ndcg", "rank:pairwise": "none"}
 
     def __init__(self, num_features: int, max_bins: int = 256, max_depth: int = 6,
                  learning_rate: float = 0.3, reg_lambda: float = 1.0, gamma: float = 0.0,
                  min_child_weight: float = 1.0, objective: str = "logistic",
-                 rank_sigma: float = 1.0, rank_normalize: str = "none", num_outputs: int = 1):
+                 rank_sigma: float = 1.0, rank_normalize: str = "none", num_outputs: int = 1,
+                 cut_weight: str = "none"):
+        if cut_weight not in ("none", "row"):
+            raise ValueError(f"cut_weight must be 'none' or 'row', got {cut_weight!r}")
+        if cut_weight == "row" and objective in self._RANK_WEIGHTING:
+            raise ValueError(f"cut_weight='row': objective {objective!r} takes no row weights")
         if objective not in ("logistic", "squared", "softmax") + tuple(self._RANK_WEIGHTING):
             raise ValueError("objective must be 'logistic', 'squared', 'softmax', 'rank:ndcg' or "
                              f"'rank:pairwise', got {objective!r}")
@@ -487,7 +500,7 @@ class SparseGBDT:
         self.reg_lambda, self.gamma = float(reg_lambda), float(gamma)
         self.min_child_weight, self.objective = float(min_child_weight), objective
         self.rank_sigma, self.rank_normalize = float(rank_sigma), rank_normalize
-        self.num_outputs = num_outputs
+        self.num_outputs, self.cut_weight = num_outputs, cut_weight
         self.cuts = None    # feature_cuts of the training data
         self.trees = []     # dicts of feature / bin / default_left / leaf
         self.margin = None  # the training rows' margins, updated by boost()
@@ -573,7 +586,12 @@ class SparseGBDT:
                         "repeated ids cannot be ruled out")
                 raise ValueError(f"SparseGBDT.fit: {what}; canonicalise the data with "
                                  "ops.sort_rows(csr, duplicates=\"sum\")")
-        self.cuts = ops.feature_cuts(csr, self.num_features, self.max_bins)
+        cut_weight = None
+        if self.cut_weight == "row":
+            cut_weight = csr.get("weight")
+            if cut_weight is None:
+                raise ValueError("SparseGBDT.fit: cut_weight='row' needs csr['weight']")
+        self.cuts = ops.feature_cuts(csr, self.num_features, self.max_bins, weight=cut_weight)
         binned = ops.bin_features(csr, self.cuts, self.num_features)
         self.trees, self.margin, self._packed = [], None, None
         label, weight = csr["label"].float(), csr.get("weight")

@@ -1420,7 +1420,61 @@ def _check_cuts(name: str, cuts: Dict, num_features: int, dev) -> None:
             raise ValueError(f"{name}: {k} must be a contiguous tensor on {dev}")
 
 
-def feature_cuts(csr: Dict, num_features: int, max_bins: int = 256) -> Dict:
+def _feature_cuts_weighted(t: Dict, rows: int, num_features: int, max_bins: int,
+                           weight: torch.Tensor, cut_ptr: torch.Tensor) -> Dict:
+    """:func:`feature_cuts` with row weights (GB1w) over the transpose ``t``;
+    ``cut_ptr``: zeros ``[F + 1]``, filled here"""
+    import math
+    dev = cut_ptr.device
+    nnz = int(t["index"].numel())
+    col_ptr = t["offset"]
+    length = col_ptr[1:] - col_ptr[:-1]
+    # where a column's cuts go before they are counted: at most min(n, B) of them
+    bound = torch.zeros_like(cut_ptr)
+    torch.cumsum(length.clamp(max=max_bins), 0, out=bound[1:])
+    # the side CSR of the columns that do not fit a workgroup's LDS
+    side_ptr = torch.zeros_like(cut_ptr)
+    fused = int(_dmlc.gbdt_cut_fused_entries())
+    torch.cumsum(torch.where(length > fused, length, torch.zeros_like(length)), 0, out=side_ptr[1:])
+    s, side_entries = torch.stack([weight.double().sum(), side_ptr[-1].double()]).tolist()
+    side_entries = int(side_entries)
+    if not math.isfinite(s):
+        raise ValueError("feature_cuts: a weight is NaN or infinite")
+    scale = 1.0
+    if s > 0.0:
+        m, k = math.frexp(s)  # s = m 2^k, m in [0.5, 1): ceil(log2 s) = k, or k - 1 at a power of two
+        scale = math.ldexp(1.0, 52 - (k - 1 if m == 0.5 else k))
+    scratch_entries = min(nnz, num_features * max_bins)
+    scratch = torch.empty(scratch_entries, dtype=torch.float32, device=dev)
+    side = (0,) * 8
+    if side_entries > 0:
+        key = torch.empty((3, side_entries), dtype=torch.int32, device=dev)  # raw, sorted, scratch
+        sw = torch.empty((2, side_entries), dtype=torch.float32, device=dev)
+        sorted_ptr = torch.empty_like(side_ptr)
+        side = (_ptr(side_ptr), side_entries, _ptr(key[0]), _ptr(sw[0]), _ptr(sorted_ptr),
+                _ptr(key[1]), _ptr(sw[1]), _ptr(key[2]))
+    columns = {"offset": col_ptr, "index": t["index"], "value": t.get("value")}
+    err = torch.zeros(2, dtype=torch.int32, device=dev)  # GB1w's bits, the row sort's
+    stream = _stream()
+    _dmlc.gbdt_cut_weighted(_describe(columns, pairs=True), nnz, (_ptr(weight), rows, scale),
+                            max_bins, _ptr(bound), _ptr(scratch), scratch_entries,
+                            _ptr(cut_ptr) + 8, side, _ptr(err), stream)
+    cut_ptr[1:].cumsum_(0)
+    total, (bad, sort_bad) = int(cut_ptr[-1].item()), err.tolist()
+    if bad & int(_dmlc.gbdt_err_weight):
+        raise ValueError("feature_cuts: a weight is NaN, infinite or negative")
+    if bad:
+        raise ValueError("feature_cuts: a value is NaN")
+    if sort_bad:
+        raise RuntimeError(f"feature_cuts: the long columns' sort failed (error {sort_bad})")
+    cut = torch.empty(total, dtype=torch.float32, device=dev)
+    _dmlc.gbdt_cut_compact(_ptr(bound), _ptr(cut_ptr), _ptr(scratch), scratch_entries,
+                           num_features, _ptr(cut), total, stream)
+    return {"cut_ptr": cut_ptr, "cut": cut}
+
+
+def feature_cuts(csr: Dict, num_features: int, max_bins: int = 256,
+                 weight: Optional[torch.Tensor] = None) -> Dict:
     """The quantile cuts of every feature of a device CSR (GB1,
     src/gpu/gbdt_kernels.hip): ``{"cut_ptr": int64 [F + 1], "cut": float32
     [total]}``, feature j's cuts ascending at ``cut[cut_ptr[j]:cut_ptr[j + 1]]``.
@@ -1442,20 +1496,53 @@ def feature_cuts(csr: Dict, num_features: int, max_bins: int = 256) -> Dict:
     shapes of :func:`transpose` (32- / 64-bit indices, a row slice).  Three
     device-to-host reads: the slice's first entry ``offset[0]``, the total
     number of cuts and the error word (a transpose that is not cached yet reads
-    the slice's ends once more)."""
+    the slice's ends once more).
+
+    ``weight`` (GB1w, src/gpu/gbdt_cut_kernels.hip): contiguous float32
+    ``[rows]`` on the CSR's device, finite and ``>= 0``, one per row of the CSR
+    (of the slice, for a row slice); anything else raises ``ValueError``, a
+    wrong dtype, shape, device or layout before any launch.  The cuts then
+    follow the weighted quantile rule, in integers: an entry of row r weighs
+    ``q = llrint(float64(w[r]) * scale)`` (ties to even), ``scale = 2**(52 -
+    ceil(log2 S))`` with ``S = sum(w)`` in float64 (1.0 for S = 0), so a weight
+    below ``0.5 / scale`` counts as 0.  With ``C(v)`` the sum of q over the
+    column's entries of value ``<= v``, ``W`` the column's total and ``T(c) =
+    c * B // W``, the distinct value ``v_k`` is a cut iff ``W > 0`` and
+    ``T(C(v_k)) > T(C(v_{k-1}))`` (``C(v_0) = 0``); a column of weight 0 has no
+    cuts.  Unit weights give the bytes of ``weight=None``, and integer weights
+    those of the unweighted call on the data with row r written ``w[r]`` times.
+
+    The weighted path has no global sort and no key array.  A column of up to
+    ``_dmlc.gbdt_cut_fused_entries()`` entries is sorted by value where it lies
+    in the transpose -- in one wave's registers up to
+    ``_dmlc.gbdt_cut_wave_entries()`` entries, else in a workgroup's LDS -- its
+    q are scanned in sorted order and the cuts picked in the same kernel; the
+    cuts wait in a scratch of at most ``min(nnz, F * B)`` floats for the
+    ``cumsum`` of their counts.  The longer columns' ``(ordered value, w)`` go
+    to a side CSR that the segmented sort of :func:`sort_rows` orders, and a
+    streaming kernel picks their cuts tile by tile; one workgroup sorts and
+    picks a whole such column, which is untimed for columns of millions of
+    entries.  Three device-to-host reads: ``S`` together with the long
+    columns' entry count, the total number of cuts, and the error words."""
     if isinstance(max_bins, bool) or not isinstance(max_bins, int) \
             or not 2 <= max_bins <= int(_dmlc.gbdt_max_bins()):
         raise ValueError(f"feature_cuts: max_bins must be an int in [2, "
                          f"{int(_dmlc.gbdt_max_bins())}], got {max_bins!r}")
     csr_u = _unpair(csr)
+    if weight is not None:
+        _check_rows("feature_cuts", "weight", weight, torch.float32,
+                    int(csr_u["offset"].numel()) - 1, csr_u["index"].device)
     t = _cached_transpose(csr, csr_u, int(num_features), "transpose")
     num_features = int(num_features)
     dev = csr_u["index"].device
     nnz = int(t["index"].numel())
+    cut_ptr = torch.zeros(num_features + 1, dtype=torch.int64, device=dev)
+    if weight is not None and nnz > 0:
+        return _feature_cuts_weighted(t, int(weight.numel()), num_features, max_bins, weight,
+                                      cut_ptr)
     off = csr_u["offset"]
     off = off.view(torch.int64) if off.dtype != torch.int64 else off
     lo = int(off[0].item()) if off.numel() > 1 else 0
-    cut_ptr = torch.zeros(num_features + 1, dtype=torch.int64, device=dev)
     if nnz == 0:
         return {"cut_ptr": cut_ptr, "cut": torch.empty(0, dtype=torch.float32, device=dev)}
     value = csr_u.get("value")

@@ -8,7 +8,9 @@ predict(method="rows")), one process on one MI355X.
     python examples/train_sparse_gbdt.py data/train.libsvm --rounds 20 --max-depth 6
 
 Without a data path a synthetic shard is generated.  An absent entry is a
-missing value: every split learns the side such rows go to.
+missing value: every split learns the side such rows go to.  --cut-weight row
+places the bins by the rows' weights (the weighted quantile cuts, GB1w); the
+data must carry a weight per row.
 """
 import argparse
 import json
@@ -29,6 +31,8 @@ def main():
     ap.add_argument("--max-bins", type=int, default=256)
     ap.add_argument("--lr", type=float, default=0.3)
     ap.add_argument("--objective", choices=("logistic", "squared"), default="logistic")
+    ap.add_argument("--cut-weight", choices=("none", "row"), default="none",
+                    help="row: quantile cuts over the rows' weights, not their count")
     args = ap.parse_args()
 
     import torch
@@ -55,10 +59,16 @@ def main():
             t[k], held[k] = whole[k][:ntrain], whole[k][ntrain:]
     label = t["label"].float()
     model = SparseGBDT(num_features, max_bins=args.max_bins, max_depth=args.max_depth,
-                       learning_rate=args.lr, objective=args.objective)
+                       learning_rate=args.lr, objective=args.objective,
+                       cut_weight=args.cut_weight)
+    cut_weight = None
+    if args.cut_weight == "row":
+        if t.get("weight") is None:
+            ap.error("--cut-weight row: the data has no row weights")
+        cut_weight = t["weight"].float().contiguous()
 
     t0 = time.perf_counter()
-    model.cuts = ops.feature_cuts(t, num_features, args.max_bins)
+    model.cuts = ops.feature_cuts(t, num_features, args.max_bins, weight=cut_weight)
     binned = ops.bin_features(t, model.cuts, num_features)
     torch.cuda.synchronize()
     t_bin = time.perf_counter() - t0

@@ -41,6 +41,8 @@
  *   U4 compact remap     LaunchCompactRemap       (compact_kernels.hip)
  *   L1 lazy row update   LaunchLazyUpdate         (optim_kernels.hip)
  *   GB1 quantile cuts    LaunchGbdtCutCount, LaunchGbdtCutEmit (gbdt_kernels.hip)
+ *   GB1w weighted cuts   LaunchGbdtCutFused, LaunchGbdtCutLong, LaunchGbdtCutCompact
+ *                        (gbdt_cut_kernels.hip; long columns through SR1 - SR3)
  *   GB2 bin features     LaunchGbdtBin            (gbdt_kernels.hip)
  *   GB3 / GB3m grad histogram LaunchGbdtHistogram (gbdt_kernels.hip)
  *   GB4 / GB4m best splits    LaunchGbdtBestSplits (gbdt_kernels.hip)
@@ -832,6 +834,63 @@ void LaunchGbdtCutCount(const int64_t* keys, const CsrView& columns, uint64_t nn
  *  cut_ptr: the exclusive scan of the counts; a position at or past capacity is not written */
 void LaunchGbdtCutEmit(const int64_t* keys, const CsrView& columns, uint64_t nnz, uint32_t max_bins,
                        const int64_t* cut_ptr, float* cut, uint64_t capacity, hipStream_t stream);
+// ------------- weighted quantile cuts (gbdt_cut_kernels.hip) -------------
+/*! \brief entries of a column GB1w sorts in one wave's registers (4 per lane) */
+constexpr uint32_t kGbdtCutWaveEntries = 256;
+/*! \brief entries of a column GB1w sorts, scans and picks whole in a workgroup's LDS;
+ *  longer columns go through the segmented row sort and a streaming pick */
+constexpr uint32_t kGbdtCutFusedEntries = 4096;
+/*! \brief bit GB1w ORs into its error word: a weight is NaN, infinite or negative */
+constexpr uint32_t kGbdtErrWeight = 2;
+/*! \brief the row weights of GB1w: weight [rows] and the power of two that quantises them,
+ *  q = llrint(double(w) * scale) */
+struct GbdtCutWeights {
+  const float* weight;
+  uint64_t rows;
+  double scale;
+};
+/*! \brief the long columns' side CSR of GB1w: ptr [num_features + 1] is the scan of the
+ *  lengths of the columns above kGbdtCutFusedEntries (0 for the others) and ends at `entries`;
+ *  key / weight [entries] are filled and sorted_* [entries], sorted_ptr [num_features + 1]
+ *  receive them sorted; sort_scratch: `entries` u32 words */
+struct GbdtCutSide {
+  const int64_t* ptr;
+  uint64_t entries;
+  uint32_t* key;
+  float* weight;
+  uint64_t* sorted_ptr;
+  uint32_t* sorted_key;
+  float* sorted_weight;
+  uint32_t* sort_scratch;
+};
+/*!
+ * \brief GB1w, columns of up to kGbdtCutFusedEntries entries of `columns` (a transpose of nnz
+ *  entries, pairs or separate arrays, value may be null: 1.0; its row ids index weights.weight).
+ *  With q = llrint(double(w[row]) * scale), C(v) the sum of q over a column's entries of value
+ *  <= v, W the column's total and T(c) = floor(c B / W), B = max_bins (2 .. 256), the distinct
+ *  value v_k is a cut iff W > 0 and T(C(v_k)) > T(C(v_{k-1})), C(v_0) = 0.  Column f's cuts go,
+ *  ascending, to scratch[bound[f] ..) -- bound [num_features + 1]: the scan of min(n_f, B),
+ *  within scratch_entries -- and their number to counts[f].  Every column's count is written
+ *  except those of the longer columns (LaunchGbdtCutLong).  The sums of q must stay below
+ *  2^62 / B: the caller picks scale so.  A NaN value ORs kGbdtErrNaN and a NaN, infinite or
+ *  negative weight of any row kGbdtErrWeight into error[0] (device words the caller zeroed).
+ */
+void LaunchGbdtCutFused(const CsrView& columns, uint64_t nnz, const GbdtCutWeights& weights,
+                        uint32_t max_bins, const int64_t* bound, float* scratch,
+                        uint64_t scratch_entries, int64_t* counts, uint32_t* error,
+                        hipStream_t stream);
+/*! \brief GB1w, the columns above kGbdtCutFusedEntries: the same cuts, through `side` and
+ *  LaunchSortRows, whose error bits go to error[1] (error: two words).  side.entries == 0
+ *  returns after the checks.  One workgroup sorts and picks a whole column. */
+void LaunchGbdtCutLong(const CsrView& columns, uint64_t nnz, const GbdtCutWeights& weights,
+                       uint32_t max_bins, const int64_t* bound, float* scratch,
+                       uint64_t scratch_entries, int64_t* counts, const GbdtCutSide& side,
+                       uint32_t* error, hipStream_t stream);
+/*! \brief GB1w, behind the scan of the counts: cut[cut_ptr[f] + k] = scratch[bound[f] + k];
+ *  a position at or past capacity is not written */
+void LaunchGbdtCutCompact(const int64_t* bound, const int64_t* cut_ptr, const float* scratch,
+                          uint64_t scratch_entries, uint64_t num_features, float* cut,
+                          uint64_t capacity, hipStream_t stream);
 /*!
  * \brief GB2: for the nnz entries of `columns` (a transpose, pairs or separate
  *  arrays, value may be null: 1.0) row_out[j] = row id and bin_out[j] =

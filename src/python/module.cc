@@ -1307,6 +1307,47 @@ PYBIND11_MODULE(_dmlc, m) {
       },
       py::arg("keys"), py::arg("columns"), py::arg("nnz"), py::arg("max_bins"), py::arg("cut_ptr"),
       py::arg("cut"), py::arg("capacity"), py::arg("stream"));
+  // GB1w: weights travel as (weight, rows, scale), the long columns' side CSR as
+  // (ptr, entries, key, weight, sorted_ptr, sorted_key, sorted_weight, sort_scratch)
+  using CutWeightsArg = std::tuple<uintptr_t, uint64_t, double>;
+  using CutSideArg = std::tuple<uintptr_t, uint64_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t,
+                                uintptr_t, uintptr_t>;
+  m.def("gbdt_cut_wave_entries", []() { return gpu::kGbdtCutWaveEntries; });
+  m.def("gbdt_cut_fused_entries", []() { return gpu::kGbdtCutFusedEntries; });
+  m.attr("gbdt_err_weight") = gpu::kGbdtErrWeight;
+  m.def(
+      "gbdt_cut_weighted",
+      [stream_of](const CsrArg& columns, uint64_t nnz, const CutWeightsArg& weights,
+                  uint32_t max_bins, uintptr_t bound, uintptr_t scratch, uint64_t scratch_entries,
+                  uintptr_t counts, const CutSideArg& side, uintptr_t error, uintptr_t stream) {
+        // the fused columns, then -- with side entries -- the long ones
+        const gpu::CsrView view = View(columns);
+        const gpu::GbdtCutWeights w{Ptr<const float>(std::get<0>(weights)), std::get<1>(weights),
+                                    std::get<2>(weights)};
+        gpu::LaunchGbdtCutFused(view, nnz, w, max_bins, Ptr<const int64_t>(bound),
+                                Ptr<float>(scratch), scratch_entries, Ptr<int64_t>(counts),
+                                Ptr<uint32_t>(error), stream_of(stream));
+        const gpu::GbdtCutSide s{Ptr<const int64_t>(std::get<0>(side)), std::get<1>(side),
+                                 Ptr<uint32_t>(std::get<2>(side)), Ptr<float>(std::get<3>(side)),
+                                 Ptr<uint64_t>(std::get<4>(side)), Ptr<uint32_t>(std::get<5>(side)),
+                                 Ptr<float>(std::get<6>(side)), Ptr<uint32_t>(std::get<7>(side))};
+        gpu::LaunchGbdtCutLong(view, nnz, w, max_bins, Ptr<const int64_t>(bound),
+                               Ptr<float>(scratch), scratch_entries, Ptr<int64_t>(counts), s,
+                               Ptr<uint32_t>(error), stream_of(stream));
+      },
+      py::arg("columns"), py::arg("nnz"), py::arg("weights"), py::arg("max_bins"),
+      py::arg("bound"), py::arg("scratch"), py::arg("scratch_entries"), py::arg("counts"),
+      py::arg("side"), py::arg("error"), py::arg("stream"));
+  m.def(
+      "gbdt_cut_compact",
+      [stream_of](uintptr_t bound, uintptr_t cut_ptr, uintptr_t scratch, uint64_t scratch_entries,
+                  uint64_t num_features, uintptr_t cut, uint64_t capacity, uintptr_t stream) {
+        gpu::LaunchGbdtCutCompact(Ptr<const int64_t>(bound), Ptr<const int64_t>(cut_ptr),
+                                  Ptr<const float>(scratch), scratch_entries, num_features,
+                                  Ptr<float>(cut), capacity, stream_of(stream));
+      },
+      py::arg("bound"), py::arg("cut_ptr"), py::arg("scratch"), py::arg("scratch_entries"),
+      py::arg("num_features"), py::arg("cut"), py::arg("capacity"), py::arg("stream"));
   m.def(
       "gbdt_bin",
       [stream_of](const CsrArg& columns, uint64_t nnz, uintptr_t cut_ptr, uintptr_t cut,
