@@ -461,7 +461,15 @@ class SparseGBDT:
     where the rows are -- for a down-sampled class, an importance-weighted log
     or de-duplicated rows with their counts as weights.  It needs a ``weight``
     in the CSR and is refused for the rank objectives, which take no row
-    weights.  The default ``"none"`` places the cuts by counting entries."""
+    weights.  The default ``"none"`` places the cuts by counting entries.
+
+    Split search (``split_search``): ``"histogram"``, the default, runs the
+    two launches above and holds the level's histogram, 16 bytes per node and
+    bin.  ``"fused"`` runs :func:`~dmlc_core_amd.ops.level_splits` instead
+    (GB9): the same splits bit for bit, hence the same trees, from scratch of
+    16 bytes per node and 4096 entries -- the way to deep levels and 256 bins
+    on a wide matrix.  Scalar leaves only: with ``num_outputs > 1`` it is
+    refused."""
 
     _RANK_WEIGHTING = {"rank:ndcg": "ndcg", "rank:pairwise": "none"}
 
@@ -469,7 +477,12 @@ class SparseGBDT:
                  learning_rate: float = 0.3, reg_lambda: float = 1.0, gamma: float = 0.0,
                  min_child_weight: float = 1.0, objective: str = "logistic",
                  rank_sigma: float = 1.0, rank_normalize: str = "none", num_outputs: int = 1,
-                 cut_weight: str = "none"):
+                 cut_weight: str = "none", split_search: str = "histogram"):
+        if split_search not in ("histogram", "fused"):
+            raise ValueError(f"split_search must be 'histogram' or 'fused', got {split_search!r}")
+        if split_search == "fused" and num_outputs != 1:
+            raise ValueError("split_search='fused' searches scalar-leaf trees; vector leaves "
+                             f"(num_outputs={num_outputs!r}) take the histogram path")
         if cut_weight not in ("none", "row"):
             raise ValueError(f"cut_weight must be 'none' or 'row', got {cut_weight!r}")
         if cut_weight == "row" and objective in self._RANK_WEIGHTING:
@@ -501,7 +514,8 @@ class SparseGBDT:
         self.min_child_weight, self.objective = float(min_child_weight), objective
         self.rank_sigma, self.rank_normalize = float(rank_sigma), rank_normalize
         self.num_outputs, self.cut_weight = num_outputs, cut_weight
-        self.cuts = None    # feature_cuts of the training data
+        self.split_search = split_search
+        self.cuts = None   # feature_cuts of the training data
         self.trees = []     # dicts of feature / bin / default_left / leaf
         self.margin = None  # the training rows' margins, updated by boost()
         self._packed = None  # ops.pack_forest of the trees, for predict(method="rows") / leaves()
@@ -641,9 +655,13 @@ class SparseGBDT:
                 (-self.learning_rate * sums[..., 0] / (sums[..., 1] + self.reg_lambda)).float()
             if depth == self.max_depth:
                 break
-            hist = histogram(binned, g, h, pos, n, scale, first_node=first)
-            split = splits(hist, node_sum, binned["cut_ptr"], scale, self.reg_lambda,
-                           self.gamma, self.min_child_weight)
+            if self.split_search == "fused":
+                split = ops.level_splits(binned, g, h, pos, node_sum, scale, self.reg_lambda,
+                                         self.gamma, self.min_child_weight, first_node=first)
+            else:
+                hist = histogram(binned, g, h, pos, n, scale, first_node=first)
+                split = splits(hist, node_sum, binned["cut_ptr"], scale, self.reg_lambda,
+                               self.gamma, self.min_child_weight)
             for k in ("feature", "bin", "default_left"):
                 tree[k][first:first + n] = split[k]
             pos = ops.advance_rows(binned, pos, split, *self._children(split, ids), first_node=first)

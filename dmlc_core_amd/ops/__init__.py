@@ -10,6 +10,8 @@ Histogram gradient-boosted trees run on the column-major binned matrix:
 :func:`grad_histogram` -> :func:`best_splits` -> :func:`advance_rows`.
 Trees with K values per leaf (multiclass, multi-target) take the K-channel
 :func:`grad_histogram_multi` -> :func:`best_splits_multi` instead.
+:func:`level_splits` is :func:`grad_histogram` -> :func:`best_splits` in one
+step that never writes the node histogram (GB9), with the same answer.
 The trained forest scores row-major batches in one launch:
 :func:`pack_forest` once, then :func:`predict_forest` for margins or leaf ids
 (GB6; GB6m sums vector leaves to ``[rows, K]`` margins in the same launch).
@@ -41,7 +43,7 @@ __all__ = ["spmv", "spmv_t", "hashed_dense", "SpMVFunction", "csr_spmv", "transp
            "qid_groups", "group_rows", "rank_loss", "rank_loss_parts", "rank_grad_hess",
            "RankLossFunction", "ndcg",
            "feature_cuts", "bin_features", "gradient_scale", "grad_histogram", "best_splits",
-           "grad_histogram_multi", "best_splits_multi",
+           "grad_histogram_multi", "best_splits_multi", "level_splits",
            "advance_rows", "pack_forest", "predict_forest"]
 
 # persistent transpose scratch per (device, stream), grow-only: a rebuild (a
@@ -1810,6 +1812,85 @@ def best_splits_multi(hist: torch.Tensor, node_sum: torch.Tensor, cut_ptr: torch
     calls give the same bytes."""
     return _best_splits("best_splits_multi", True, hist, node_sum, cut_ptr, scale, reg_lambda, gamma,
                         min_child_weight)
+
+
+def _long_columns(binned: Dict, arg: tuple) -> tuple:
+    """GB9's list of the columns of more than a segment's entries, as the binding takes it
+    (gpu::GbdtLongColumns); made once per binned matrix and kept on the dict"""
+    key = (arg[0], arg[3], arg[4], arg[5])  # the offset and cut_ptr arrays it was made from
+    cached = binned.get("_long_columns")
+    if cached is not None and cached[0] == key:
+        return cached[1]
+    dev, cap = binned["row"].device, arg[5] // int(_dmlc.gbdt_segment_entries())
+    lc, keep = (0, 0, 0, 0, 0, 0), ()
+    if cap > 0:
+        column = torch.empty(cap, dtype=torch.int64, device=dev)
+        sums = torch.empty((2, cap + 1), dtype=torch.int64, device=dev)
+        totals = torch.empty(3, dtype=torch.int64, device=dev)
+        _dmlc.gbdt_long_columns(arg, cap, _ptr(column), _ptr(sums[0]), _ptr(sums[1]), _ptr(totals),
+                                _stream())
+        count, bins, pieces = totals.tolist()  # the one device-to-host read
+        if count > 0:
+            lc, keep = (_ptr(column), _ptr(sums[0]), _ptr(sums[1]), count, bins, pieces), (column, sums)
+    binned["_long_columns"] = (key, lc, keep)
+    return lc
+
+
+def level_splits(binned: Dict, grad: torch.Tensor, hess: torch.Tensor, pos: torch.Tensor,
+                 node_sum: torch.Tensor, scale: float, reg_lambda: float = 1.0, gamma: float = 0.0,
+                 min_child_weight: float = 1.0, first_node: int = 0) -> Dict:
+    """The best split of every node of a tree level without the node histogram
+    (GB9): the dict of :func:`best_splits`, and every tensor of it
+    ``torch.equal`` to ``best_splits(grad_histogram(binned, grad, hess, pos, N,
+    scale, first_node), node_sum, binned["cut_ptr"], scale, reg_lambda, gamma,
+    min_child_weight)`` with ``N = node_sum.shape[0]`` -- the sums are the same
+    integers and the gains the same float64 expression under the same total
+    order.  Scalar gradients only.
+
+    The histogram ``[N, total_bins, 2]`` (16 bytes per node and bin) is never
+    formed.  One workgroup per ``_dmlc.gbdt_segment_entries()`` entries owns the
+    columns of at most that many entries that start in its stretch, sums them
+    per (node, bin) in LDS as :func:`grad_histogram` does (tiling the nodes
+    when they do not fit) and scans the sums there for the best threshold of
+    each node, one lane per (node, column); it leaves 16 bytes per node.  The
+    few longer columns are summed by pieces into a spill histogram of their
+    bins alone and scanned from it.  Their list is made once per ``binned``
+    (one small launch and device-to-host read) and kept on the dict under
+    ``"_long_columns"``.  Scratch stays within a fixed budget: a level whose
+    nodes need more is searched in consecutive node windows, with the same
+    answer.  Nothing else is read back."""
+    name = "level_splits"
+    arg = _binned_arg(name, binned)
+    rows, total, dev = arg[6], arg[7], binned["row"].device
+    for what, t in (("grad", grad), ("hess", hess)):
+        if isinstance(t, torch.Tensor) and t.dim() == 2:
+            raise ValueError(f"{name}: {what} is [rows, K]; vector-leaf trees take "
+                             "grad_histogram_multi / best_splits_multi")
+        _check_rows(name, what, t, torch.float32, rows, dev)
+    _check_rows(name, "pos", pos, torch.int32, rows, dev)
+    if not isinstance(node_sum, torch.Tensor) or node_sum.dtype != torch.int64 \
+            or node_sum.dim() != 2 or node_sum.shape[1] != 2 or node_sum.device != dev \
+            or not node_sum.is_contiguous():
+        raise ValueError(f"{name}: node_sum must be a contiguous int64 tensor [N, 2] on {dev}")
+    n = int(node_sum.shape[0])
+    _check_window(name, n, first_node)
+    if not float(reg_lambda) > 0:
+        raise ValueError(f"{name}: reg_lambda must be > 0, got {reg_lambda!r}")
+    if not float(scale) > 0:
+        raise ValueError(f"{name}: scale must be > 0, got {scale!r}")
+    res = {"feature": torch.full((n,), -1, dtype=torch.int64, device=dev),
+           "bin": torch.zeros(n, dtype=torch.int32, device=dev),
+           "default_left": torch.zeros(n, dtype=torch.bool, device=dev),
+           "gain": torch.zeros(n, dtype=torch.float64, device=dev)}
+    if rows > 0 and total > 0 and arg[5] > 0:
+        lc = _long_columns(binned, arg)
+        ws = _workspace(int(_dmlc.gbdt_level_scratch_bytes(n, arg[5], lc)) + 16, dev)
+        _dmlc.gbdt_level_splits(arg, lc, _ptr(grad), _ptr(hess), _ptr(pos), first_node, n,
+                                _ptr(node_sum), float(scale), float(reg_lambda), float(gamma),
+                                float(min_child_weight), (_ptr(ws) + 15) // 16 * 16,
+                                _ptr(res["feature"]), _ptr(res["bin"]), _ptr(res["default_left"]),
+                                _ptr(res["gain"]), _stream())
+    return res
 
 
 def advance_rows(binned: Dict, pos: torch.Tensor, split: Dict, left: torch.Tensor,

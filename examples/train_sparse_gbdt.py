@@ -33,6 +33,8 @@ def main():
     ap.add_argument("--objective", choices=("logistic", "squared"), default="logistic")
     ap.add_argument("--cut-weight", choices=("none", "row"), default="none",
                     help="row: quantile cuts over the rows' weights, not their count")
+    ap.add_argument("--split-search", choices=("histogram", "fused"), default="histogram",
+                    help="fused: ops.level_splits, the same trees without the level's histogram")
     args = ap.parse_args()
 
     import torch
@@ -60,7 +62,7 @@ def main():
     label = t["label"].float()
     model = SparseGBDT(num_features, max_bins=args.max_bins, max_depth=args.max_depth,
                        learning_rate=args.lr, objective=args.objective,
-                       cut_weight=args.cut_weight)
+                       cut_weight=args.cut_weight, split_search=args.split_search)
     cut_weight = None
     if args.cut_weight == "row":
         if t.get("weight") is None:

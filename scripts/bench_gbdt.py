@@ -42,6 +42,14 @@ cuts for each of 1 M features 64 nodes would need 262 GB.
              histogram), which is how the same sums were had without them.  The
              histograms are compared exactly
 
+  --fused    instead of the sections after `one-time`: ops.level_splits (GB9) against
+             ops.grad_histogram + ops.best_splits at each of --nodes, their windows
+             alternating, and the outputs compared exactly; then a depth-6
+             SparseGBDT.boost with split_search "fused" and "histogram" (the trees
+             compared).  `peak_allocated_gb`: torch's peak during one level_splits
+             call, the shard, the binned matrix and the scratch included.
+             --fused only: level_splits alone, for a shape whose histogram does not fit
+
 Every figure is the median (and the fastest, the slowest) of --iters host-clock windows
 around one call each, ending in a device synchronise, after one warm-up call.
 Prints one JSON object; a line per section goes to stderr.
@@ -72,10 +80,13 @@ def main():
     ap.add_argument("--vector-leaves", default="", help="the predict section: these K too")
     ap.add_argument("--outputs", type=int, default=0,
                     help="K > 0: only the one-time section and the K-output ops")
+    ap.add_argument("--fused", nargs="?", const="on", default="off", choices=("off", "on", "only"),
+                    help="only the one-time section and ops.level_splits (GB9) against "
+                         "grad_histogram + best_splits; 'only': without the two-step path")
     args = ap.parse_args()
     import torch
 
-    from dmlc_core_amd import data, ops
+    from dmlc_core_amd import _dmlc, data, ops
     from dmlc_core_amd.models import SparseGBDT
 
     assert torch.cuda.is_available(), "bench_gbdt.py measures on a GPU"
@@ -223,6 +234,56 @@ def main():
             res[f"splits_found_multi_{n}"] = int((split["feature"] >= 0).sum())
             del hist, per_k, node_sum, sums_k
             torch.cuda.empty_cache()
+        print(json.dumps(res), flush=True)
+        return
+
+    # ------------------------------------------- fused level search (--fused only)
+    if args.fused != "off":
+        g = torch.randn(rows, device=dev, generator=gen)
+        h = torch.rand(rows, device=dev, generator=gen)
+        scale = ops.gradient_scale(g, h)
+        qgh = torch.stack([torch.round(g.double() * scale), torch.round(h.double() * scale)],
+                          1).long()
+        cut_ptr = binned["cut_ptr"]
+        lens = binned["offset"][1:] - binned["offset"][:-1]
+        res["long_columns"] = int((lens > int(_dmlc.gbdt_segment_entries())).sum())
+        del lens
+        for n in (int(s) for s in args.nodes.split(",")):
+            pos = torch.randint(0, n, (rows,), device=dev, generator=gen, dtype=torch.int32)
+            node_sum = torch.zeros((n, 2), dtype=torch.int64, device=dev)
+            node_sum.index_add_(0, pos.long(), qgh)
+
+            def fused():
+                return ops.level_splits(binned, g, h, pos, node_sum, scale)
+
+            def two_step():
+                return ops.best_splits(ops.grad_histogram(binned, g, h, pos, n, scale), node_sum,
+                                       cut_ptr, scale)
+            if args.fused == "only":  # a shape whose histogram does not fit
+                r = timed(fused)
+            else:
+                r, r1 = timed_pair(fused, two_step)
+                note(f"histogram_then_best_splits_{n}", r1)
+                res[f"two_step_over_fused_{n}"] = ratio(r1, r)
+                got, want = fused(), two_step()
+                res[f"level_splits_{n}_equal"] = all(torch.equal(got[k], want[k]) for k in got)
+            r["hist_gb"] = round(n * total * 16 / 1e9, 2)
+            torch.cuda.empty_cache()
+            torch.cuda.reset_peak_memory_stats()
+            fused()  # its workspace is warm: the figure is what stays allocated, scratch included
+            torch.cuda.synchronize()
+            r["peak_allocated_gb"] = round(torch.cuda.max_memory_allocated() / 1e9, 3)
+            note(f"level_splits_{n}", r)
+            res[f"splits_found_{n}"] = int((fused()["feature"] >= 0).sum())
+            torch.cuda.empty_cache()
+        if args.fused == "on":
+            models = [SparseGBDT(feats, max_bins=args.max_bins, max_depth=6, split_search=s)
+                      for s in ("fused", "histogram")]
+            r, r1 = timed_pair(*(lambda m=m: m.boost(binned, csr["label"]) for m in models))
+            note("boost_depth6_fused", r)
+            note("boost_depth6_histogram", r1)
+            res["boost_trees_equal"] = all(
+                torch.equal(a[k], b[k]) for a, b in zip(models[0].trees, models[1].trees) for k in a)
         print(json.dumps(res), flush=True)
         return
 

@@ -26,6 +26,11 @@
  *                      launcher, which picks the kernel by its num_outputs
  *                      (kGbdtScalar: GB3 / GB4), and shares its cell arithmetic
  *                      (add_to_cell, flush_cell) and candidate key (split_key).
+ *  GB9 k_gbdt_level_*  GB3 and GB4 of one level fused: a workgroup owns whole columns,
+ *                      sums them in LDS and scans the sums there for the best
+ *                      thresholds, so no node histogram is written; columns
+ *                      longer than a segment go through a small spill histogram.
+ *                      Described at the kernels; the answer is GB4's, bit for bit.
  *
  *  Segments.  The entries of the column-major matrix, in storage order, are
  *  cut every kGbdtSegmentEntries: workgroup s owns entries [s S, (s + 1) S).
@@ -470,6 +475,334 @@ __global__ __launch_bounds__(kThreads) void k_gbdt_split_pick(const Cand* __rest
   }
 }
 
+// ---------------------------------------------------------------- GB9
+/*! \brief the first k in [0, n] with ptr[k] >= x; ptr [n + 1] ascends from ptr[0] >= 0 */
+__device__ __forceinline__ int64_t first_ge(const int64_t* __restrict__ ptr, int64_t n, int64_t x) {
+  if (x <= ptr[0]) return 0;
+  return last_le(ptr, 0, n, x - 1) + 1;
+}
+
+/*! \brief stage_columns for GB9: col_ptr[f_lo .. f_end] - base clamped to [0, 2 kSeg], the span of
+ *  the entries a workgroup owns (short columns that start inside one segment) */
+__device__ __forceinline__ bool stage_owned_columns(const int64_t* __restrict__ col_ptr, int64_t f_lo,
+                                                    int64_t f_end, int64_t base, uint32_t* s_col) {
+  const int64_t n = f_end - f_lo + 1;
+  if (n > kColsLds) return false;
+  for (int64_t k = threadIdx.x; k < n; k += kThreads) {
+    const int64_t d = col_ptr[f_lo + k] - base;
+    s_col[k] = static_cast<uint32_t>(d < 0 ? 0 : (d > 2 * kSeg ? 2 * kSeg : d));
+  }
+  __syncthreads();
+  return true;
+}
+
+/*! \brief k_gbdt_split_scan's walk over the nc (g, h) cells at h (LDS or global) of feature f
+ *  under the node sums (ng, nh): the same statements, so the same bits in every gain */
+__device__ __forceinline__ Cand scan_cells(const long long* h, int64_t nc, int64_t f, long long ng,
+                                           long long nh, double scale, double reg_lambda,
+                                           double gamma, double min_child_weight) {
+  Cand best{0.0, kNoKey};
+  long long tg = 0, th = 0;
+  for (int64_t t = 0; t < nc; ++t) {
+    tg += h[2 * t];
+    th += h[2 * t + 1];
+  }
+  const long long miss_g = ng - tg, miss_h = nh - th;  // rows without an entry in f
+  const double g_all = static_cast<double>(ng) / scale, h_all = static_cast<double>(nh) / scale;
+  const double parent = g_all * g_all / (h_all + reg_lambda);
+  long long lg = 0, lh = 0;
+  for (int64_t t = 0; t < nc; ++t) {
+    lg += h[2 * t];
+    lh += h[2 * t + 1];
+    for (int dir = 0; dir < 2; ++dir) {  // 0: missing goes right, 1: left
+      const long long qgl = lg + (dir != 0 ? miss_g : 0ll), qhl = lh + (dir != 0 ? miss_h : 0ll);
+      const double gl = static_cast<double>(qgl) / scale, hl = static_cast<double>(qhl) / scale;
+      const double gr = static_cast<double>(ng - qgl) / scale;
+      const double hr = static_cast<double>(nh - qhl) / scale;
+      if (!(hl >= min_child_weight && hr >= min_child_weight)) continue;
+      const double gain =
+          0.5 * (gl * gl / (hl + reg_lambda) + gr * gr / (hr + reg_lambda) - parent) - gamma;
+      if (gain > 0.0) best = better(best, Cand{gain, split_key(f, t, dir)});
+    }
+  }
+  return best;
+}
+
+/*! \brief the level's constants of the split search */
+struct LevelGain {
+  const long long* node_sum;
+  double scale, reg_lambda, gamma, min_child_weight;
+};
+
+/*!
+ * \brief GB9, the short columns: histogram and split search of a level in one launch, without
+ *  the node histogram.
+ *
+ *  Ownership.  Workgroup s owns the columns of 1 .. kSeg entries (and the empty ones) whose
+ *  first entry lies in [s S, (s + 1) S): whole columns, so their (node, bin) sums are complete
+ *  in its LDS.  It streams them to their end, fewer than 2 S entries; a longer column that
+ *  starts there is the last of the range and belongs to the spill kernels below.  The grid has
+ *  nnz / S + 1 workgroups, so that empty columns behind the last entry have an owner too.
+ *
+ *  Passes.  As GB3: groups of consecutive columns whose W cells fit the table, and passes of
+ *  as many nodes as fit.  The cells of a node lie W | 1 apart, an odd number of 16-byte cells.
+ *
+ *  Scan.  After a pass one lane per (node of the pass, column of the group) walks the column's
+ *  cells in LDS.  A wave takes a contiguous quarter of the pass's nodes; within it the lanes run
+ *  over the columns first and the nodes second (lane = node x ncol + column), a whole number of
+ *  nodes per step.  Lanes on neighbouring columns of a node read cells that lie the columns' cut
+ *  counts apart, and lanes on neighbouring nodes cells that lie W | 1 apart: with the node stride
+ *  W itself, every W that is a multiple of 16 cells (256 bytes, all 64 banks) would put the lanes
+ *  of one column, one per node, on the same banks at every step -- 21 ways for three 16-bin
+ *  columns.  The odd stride spreads 16 neighbouring nodes over all banks, at the price of one
+ *  cell per node (14 instead of 15 nodes of a 256-cut column per pass).  The candidates of a node
+ *  meet by a segmented shuffle reduction under better(), and the segment's first lane folds the
+ *  result into partial[node, s] by a plain load and store: the workgroup is the only writer of
+ *  its slots, and its own accesses are ordered by the barriers between the passes.
+ */
+__global__ __launch_bounds__(kThreads) void k_gbdt_level_short(
+    const int64_t* __restrict__ col_ptr, const int32_t* __restrict__ row,
+    const uint8_t* __restrict__ bin, int64_t nnz, int64_t nfeat, const int64_t* __restrict__ cut_ptr,
+    int64_t total_bins, const float* __restrict__ grad, const float* __restrict__ hess,
+    const int32_t* __restrict__ pos, int64_t rows, int32_t first_node, int32_t num_nodes,
+    LevelGain lg, Cand* partial, int64_t nparts) {
+  __shared__ unsigned long long s_acc[2 * kGbdtCells];
+  __shared__ uint32_t s_col[kColsLds];
+  __shared__ int64_t s_slot;
+  const Cand none{0.0, kNoKey};
+  for (int64_t n = threadIdx.x; n < num_nodes; n += kThreads) partial[n * nparts + blockIdx.x] = none;
+  const int64_t base = static_cast<int64_t>(blockIdx.x) * kSeg;
+  int64_t a = 0, b = 0;
+  if (threadIdx.x == 0) {
+    a = first_ge(col_ptr, nfeat, base);
+    b = first_ge(col_ptr, nfeat, base + kSeg);
+    if (b > a && col_ptr[b] - col_ptr[b - 1] > kSeg) --b;  // a long column: the spill path's
+  }
+  const int64_t f_lo = block_bcast(a, &s_slot);
+  const int64_t f_end = block_bcast(b, &s_slot);
+  if (f_lo >= f_end) return;  // no short column starts here
+  const int64_t e_first = col_ptr[f_lo];
+  const bool staged = stage_owned_columns(col_ptr, f_lo, f_end, e_first, s_col);
+  int64_t room = kGbdtCells / num_nodes - 1;  // W <= room: every node in one pass
+  if (room < static_cast<int64_t>(kGbdtMaxBins)) room = kGbdtMaxBins;
+  const int lane = dev::lane_id(), wave = threadIdx.x / dev::kWave;
+  for (int64_t fa = f_lo; fa < f_end;) {
+    const int64_t fb = group_end(cut_ptr, fa, f_end, room, &s_slot);
+    const int64_t c0 = cut_ptr[fa];
+    const int64_t width = cut_ptr[fb] - c0;
+    const int64_t e0 = col_ptr[fa] > 0 ? col_ptr[fa] : 0;
+    const int64_t e1 = col_ptr[fb] < nnz ? col_ptr[fb] : nnz;
+    if (width > 0 && width < kGbdtCells && c0 >= 0 && c0 + width <= total_bins) {
+      const int64_t stride = width | 1;
+      int64_t per_pass = kGbdtCells / stride;
+      if (per_pass > num_nodes) per_pass = num_nodes;
+      const int64_t ncol = fb - fa;
+      for (int64_t n0 = 0; n0 < num_nodes; n0 += per_pass) {
+        const int64_t nn = n0 + per_pass <= num_nodes ? per_pass : num_nodes - n0;
+        for (int64_t i = threadIdx.x; i < 2 * nn * stride; i += kThreads) s_acc[i] = 0ull;
+        __syncthreads();
+        for (int64_t j = e0 + threadIdx.x; j < e1; j += kThreads) {
+          const int64_t f = column_of(staged, s_col, col_ptr, f_lo, fa, fb, e_first, j);
+          const int64_t cl = cut_ptr[f] - c0;
+          const int64_t nc = cut_ptr[f + 1] - cut_ptr[f];
+          const int64_t bj = bin[j];
+          const uint64_t r = static_cast<uint32_t>(row[j]);
+          if (cl < 0 || bj >= nc || cl + bj >= width || r >= static_cast<uint64_t>(rows)) continue;
+          const int64_t node = static_cast<int64_t>(pos[r]) - first_node - n0;
+          if (node < 0 || node >= nn) continue;
+          add_to_cell(s_acc, node * stride + cl + bj, grad[r], hess[r], lg.scale);
+        }
+        __syncthreads();
+        // the scan: this wave's nodes [w_lo, w_hi) of the pass
+        const int64_t share = (nn + kWaves - 1) / kWaves;
+        const int64_t w_lo = wave * share;
+        const int64_t w_hi = w_lo + share < nn ? w_lo + share : nn;
+        auto scan = [&](int64_t ln, int64_t f) -> Cand {
+          const int64_t cl = cut_ptr[f] - c0;
+          const int64_t nc = cut_ptr[f + 1] - cut_ptr[f];
+          if (cl < 0 || nc <= 0 || nc > static_cast<int64_t>(kGbdtMaxBins) || cl + nc > width) {
+            return none;
+          }
+          const long long* const cells = reinterpret_cast<const long long*>(s_acc);
+          return scan_cells(cells + 2 * (ln * stride + cl), nc, f, lg.node_sum[2 * (n0 + ln)],
+                            lg.node_sum[2 * (n0 + ln) + 1], lg.scale, lg.reg_lambda, lg.gamma,
+                            lg.min_child_weight);
+        };
+        auto keep = [&](int64_t ln, const Cand& c) {
+          if (c.key == kNoKey) return;
+          Cand* const slot = partial + (n0 + ln) * nparts + blockIdx.x;
+          *slot = better(*slot, c);
+        };
+        if (ncol <= dev::kWave) {
+          const int nc_lanes = static_cast<int>(ncol);
+          const int per_step = dev::kWave / nc_lanes;  // whole nodes per step of the wave
+          const int sub = lane / nc_lanes, col = lane % nc_lanes;
+          for (int64_t k0 = w_lo; k0 < w_hi; k0 += per_step) {
+            const int64_t ln = k0 + sub;
+            const bool active = sub < per_step && ln < w_hi;
+            Cand c = active ? scan(ln, fa + col) : none;
+            for (int d = 1; d < nc_lanes; d <<= 1) {
+              Cand o;
+              o.gain = __shfl_down(c.gain, d, dev::kWave);
+              o.key = __shfl_down(c.key, d, dev::kWave);
+              if (col + d < nc_lanes) c = better(c, o);
+            }
+            if (active && col == 0) keep(ln, c);
+          }
+        } else {
+          for (int64_t ln = w_lo; ln < w_hi; ++ln) {
+            Cand c = none;
+            for (int64_t col = lane; col < ncol; col += dev::kWave) c = better(c, scan(ln, fa + col));
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) {
+              Cand o;
+              o.gain = __shfl_xor(c.gain, d, dev::kWave);
+              o.key = __shfl_xor(c.key, d, dev::kWave);
+              c = better(c, o);
+            }
+            if (lane == 0) keep(ln, c);
+          }
+        }
+        __syncthreads();
+      }
+    }
+    fa = fb;
+  }
+}
+
+/*!
+ * \brief GB9, the list of the long columns (more than kSeg entries), made once per matrix by one
+ *  workgroup: column[i], and the running sums bin_ptr[i] of their cut counts and piece_ptr[i] of
+ *  their pieces of kSeg entries, i < capacity; totals = (columns, bins, pieces).  The waves flag
+ *  256 columns at a time by ballot and thread 0 appends the flagged ones in order.
+ */
+__global__ __launch_bounds__(kThreads) void k_gbdt_long_columns(
+    const int64_t* __restrict__ col_ptr, const int64_t* __restrict__ cut_ptr, int64_t nfeat,
+    int64_t capacity, int64_t* __restrict__ column, int64_t* __restrict__ bin_ptr,
+    int64_t* __restrict__ piece_ptr, int64_t* __restrict__ totals) {
+  __shared__ unsigned long long s_mask[kWaves];
+  int64_t count = 0, bins = 0, pieces = 0;  // thread 0's
+  for (int64_t f0 = 0; f0 < nfeat; f0 += kThreads) {
+    const int64_t f = f0 + threadIdx.x;
+    const unsigned long long mask = __ballot(f < nfeat && col_ptr[f + 1] - col_ptr[f] > kSeg);
+    if (dev::lane_id() == 0) s_mask[threadIdx.x / dev::kWave] = mask;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      for (int w = 0; w < kWaves; ++w) {
+        for (unsigned long long m = s_mask[w]; m != 0ull && count < capacity; m &= m - 1ull) {
+          const int64_t g = f0 + w * dev::kWave + __builtin_ctzll(m);
+          int64_t nc = cut_ptr[g + 1] - cut_ptr[g];
+          if (nc < 0 || nc > static_cast<int64_t>(kGbdtMaxBins)) nc = 0;
+          column[count] = g;
+          bin_ptr[count] = bins;
+          piece_ptr[count] = pieces;
+          ++count;
+          bins += nc;
+          pieces += (col_ptr[g + 1] - col_ptr[g] + kSeg - 1) / kSeg;
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    bin_ptr[count] = bins;
+    piece_ptr[count] = pieces;
+    totals[0] = count;
+    totals[1] = bins;
+    totals[2] = pieces;
+  }
+}
+
+/*! \brief GB9: clears the spill histogram */
+__global__ __launch_bounds__(kThreads) void k_gbdt_level_clear(unsigned long long* __restrict__ p,
+                                                               int64_t n) {
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * kThreads;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x; i < n; i += stride) {
+    p[i] = 0ull;
+  }
+}
+
+/*!
+ * \brief GB9, the long columns' sums: workgroup p takes piece p (kSeg entries of one long
+ *  column), sums it as GB3 does and adds its non-zero cells to spill [N x spill_bins x 2], where
+ *  the column's bins start at bin_ptr[i], with one 64-bit atomic each
+ */
+__global__ __launch_bounds__(kThreads) void k_gbdt_level_long_hist(
+    const int64_t* __restrict__ col_ptr, const int32_t* __restrict__ row,
+    const uint8_t* __restrict__ bin, int64_t nnz, const int64_t* __restrict__ cut_ptr,
+    int64_t total_bins, const float* __restrict__ grad, const float* __restrict__ hess,
+    const int32_t* __restrict__ pos, int64_t rows, int32_t first_node, int32_t num_nodes, double scale,
+    const int64_t* __restrict__ column, const int64_t* __restrict__ bin_ptr,
+    const int64_t* __restrict__ piece_ptr, int64_t count, int64_t spill_bins,
+    unsigned long long* __restrict__ spill) {
+  __shared__ unsigned long long s_acc[2 * kGbdtCells];
+  __shared__ int64_t s_slot;
+  const int64_t piece = blockIdx.x;
+  const int64_t li =
+      block_bcast(threadIdx.x == 0 ? last_le(piece_ptr, 0, count, piece) : 0, &s_slot);
+  const int64_t f = column[li];
+  const int64_t c0 = cut_ptr[f], width = cut_ptr[f + 1] - c0, sb = bin_ptr[li];
+  if (width <= 0 || width > static_cast<int64_t>(kGbdtMaxBins) || c0 < 0 ||
+      c0 + width > total_bins || sb < 0 || sb + width > spill_bins) {
+    return;
+  }
+  int64_t e0 = col_ptr[f] + (piece - piece_ptr[li]) * kSeg;
+  int64_t e1 = e0 + kSeg < col_ptr[f + 1] ? e0 + kSeg : col_ptr[f + 1];
+  if (e0 < 0) e0 = 0;
+  if (e1 > nnz) e1 = nnz;
+  int64_t per_pass = kGbdtCells / width;
+  if (per_pass > num_nodes) per_pass = num_nodes;
+  for (int64_t n0 = 0; n0 < num_nodes; n0 += per_pass) {
+    const int64_t nn = n0 + per_pass <= num_nodes ? per_pass : num_nodes - n0;
+    const int64_t cells = nn * width;
+    for (int64_t i = threadIdx.x; i < 2 * cells; i += kThreads) s_acc[i] = 0ull;
+    __syncthreads();
+    for (int64_t j = e0 + threadIdx.x; j < e1; j += kThreads) {
+      const int64_t bj = bin[j];
+      const uint64_t r = static_cast<uint32_t>(row[j]);
+      if (bj >= width || r >= static_cast<uint64_t>(rows)) continue;
+      const int64_t node = static_cast<int64_t>(pos[r]) - first_node - n0;
+      if (node < 0 || node >= nn) continue;
+      add_to_cell(s_acc, node * width + bj, grad[r], hess[r], scale);
+    }
+    __syncthreads();
+    const uint32_t width32 = static_cast<uint32_t>(width);
+    for (uint32_t i = threadIdx.x; i < static_cast<uint32_t>(cells); i += kThreads) {
+      const int64_t node = i / width32, lb = i % width32;
+      flush_cell(spill + 2 * ((n0 + node) * spill_bins + sb + lb), s_acc[2 * i], s_acc[2 * i + 1],
+                 false);
+    }
+    __syncthreads();
+  }
+}
+
+/*! \brief GB9, the long columns' candidates: GB4's lane per (node, column) over the spill
+ *  histogram, keyed by the true feature id, to the slots behind the short columns' */
+__global__ __launch_bounds__(kThreads) void k_gbdt_level_long_scan(
+    const long long* __restrict__ spill, const int64_t* __restrict__ cut_ptr, int64_t total_bins,
+    const int64_t* __restrict__ column, const int64_t* __restrict__ bin_ptr, int64_t count,
+    int64_t spill_bins, LevelGain lg, Cand* __restrict__ partial, int64_t nparts, int64_t part0) {
+  const int64_t li = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+  const int64_t node = blockIdx.y;
+  Cand best{0.0, kNoKey};
+  if (li < count) {
+    const int64_t f = column[li];
+    const int64_t c0 = cut_ptr[f], sb = bin_ptr[li];
+    int64_t nc = cut_ptr[f + 1] - c0;
+    if (c0 < 0 || c0 + nc > total_bins || nc > static_cast<int64_t>(kGbdtMaxBins) || sb < 0 ||
+        sb + nc > spill_bins) {
+      nc = 0;
+    }
+    if (nc > 0) {
+      best = scan_cells(spill + 2 * (node * spill_bins + sb), nc, f, lg.node_sum[2 * node],
+                        lg.node_sum[2 * node + 1], lg.scale, lg.reg_lambda, lg.gamma,
+                        lg.min_child_weight);
+    }
+  }
+  best = block_best(best);
+  if (threadIdx.x == 0) partial[node * nparts + part0 + blockIdx.x] = best;
+}
+
 // ---------------------------------------------------------------- GB5
 __global__ __launch_bounds__(kThreads) void k_gbdt_advance_rows(
     const int32_t* __restrict__ pos_in, int64_t rows, const int64_t* __restrict__ feature,
@@ -819,6 +1152,97 @@ void LaunchGbdtBestSplits(const int64_t* hist, const int64_t* node_sum, const in
   hipLaunchKernelGGL(k_gbdt_split_pick, dim3(num_nodes), block, 0, stream, partial,
                      static_cast<int64_t>(parts), feature, bin, default_left, gain);
   DMLC_HIP_CHECK_LAUNCH();
+}
+
+void LaunchGbdtLongColumns(const GbdtBinned& m, uint64_t capacity, int64_t* column, int64_t* bin_ptr,
+                           int64_t* piece_ptr, int64_t* totals, hipStream_t stream) {
+  CheckBinned("gbdt long columns", m.nnz, m.num_features);
+  CHECK_GE(capacity, m.nnz / kSeg) << "gbdt long columns: capacity below nnz / segment entries";
+  hipLaunchKernelGGL(k_gbdt_long_columns, dim3(1), dim3(kThreads), 0, stream, m.offset, m.cut_ptr,
+                     static_cast<int64_t>(m.num_features), static_cast<int64_t>(capacity), column,
+                     bin_ptr, piece_ptr, totals);
+  DMLC_HIP_CHECK_LAUNCH();
+}
+
+namespace {
+/*! \brief slots of `partial` per node: the short columns' workgroups, then the long columns' */
+uint64_t LevelParts(uint64_t nnz, uint64_t long_count) {
+  return nnz / kSeg + 1 + (long_count + kThreads - 1) / kThreads;
+}
+}  // namespace
+
+uint32_t GbdtLevelWindowNodes(uint64_t num_nodes, uint64_t nnz, const GbdtLongColumns& lc) {
+  const uint64_t per_node = sizeof(Cand) * (LevelParts(nnz, lc.count) + lc.bins);
+  uint64_t window = kGbdtLevelScratchBudget / per_node;
+  if (window < 1) window = 1;
+  return static_cast<uint32_t>(window < num_nodes ? window : num_nodes);
+}
+
+size_t GbdtLevelScratchBytes(uint64_t num_nodes, uint64_t nnz, const GbdtLongColumns& lc) {
+  return sizeof(Cand) * (LevelParts(nnz, lc.count) + lc.bins) *
+         GbdtLevelWindowNodes(num_nodes, nnz, lc);
+}
+
+void LaunchGbdtLevelSplits(const GbdtBinned& m, const GbdtLongColumns& lc, const float* grad,
+                           const float* hess, const int32_t* pos, int32_t first_node,
+                           uint32_t num_nodes, const int64_t* node_sum, double scale,
+                           double reg_lambda, double gamma, double min_child_weight, void* scratch,
+                           int64_t* feature, int32_t* bin, uint8_t* default_left, double* gain,
+                           hipStream_t stream) {
+  const char* const op = "gbdt level splits";
+  CheckLevel(op, m.nnz, m.num_features, num_nodes >= 1 && num_nodes <= kGbdtMaxNodes, kGbdtScalar);
+  CHECK(reg_lambda > 0.0 && scale > 0.0) << op << ": reg_lambda and scale must be > 0";
+  CHECK(Aligned16(scratch)) << op << ": scratch must be 16-byte aligned";
+  CHECK(m.nnz > 0 && m.rows > 0) << op << ": an empty matrix has no splits to search";
+  CHECK(lc.count <= m.nnz / kSeg && lc.pieces <= m.nnz / kSeg + lc.count &&
+        lc.bins <= lc.count * kGbdtMaxBins)
+      << op << ": not the long columns of this matrix";
+  const int64_t nnz = static_cast<int64_t>(m.nnz), nfeat = static_cast<int64_t>(m.num_features);
+  const int64_t total = static_cast<int64_t>(m.total_bins), rows = static_cast<int64_t>(m.rows);
+  const int64_t count = static_cast<int64_t>(lc.count), spill_bins = static_cast<int64_t>(lc.bins);
+  const uint32_t segs = static_cast<uint32_t>(m.nnz / kSeg + 1);
+  const uint32_t long_parts = static_cast<uint32_t>((lc.count + kThreads - 1) / kThreads);
+  const int64_t parts = static_cast<int64_t>(LevelParts(m.nnz, lc.count));
+  const uint32_t window = GbdtLevelWindowNodes(num_nodes, m.nnz, lc);
+  const dim3 block(kThreads);
+  Cand* const partial = static_cast<Cand*>(scratch);
+  for (uint32_t w0 = 0; w0 < num_nodes; w0 += window) {
+    const uint32_t nw = num_nodes - w0 < window ? num_nodes - w0 : window;
+    const int32_t first = first_node + static_cast<int32_t>(w0), nodes = static_cast<int32_t>(nw);
+    const LevelGain lg{reinterpret_cast<const long long*>(node_sum) + 2 * w0, scale, reg_lambda,
+                       gamma, min_child_weight};
+    hipLaunchKernelGGL(k_gbdt_level_short, dim3(segs), block, 0, stream, m.offset, m.row, m.bin, nnz,
+                       nfeat, m.cut_ptr, total, grad, hess, pos, rows, first, nodes, lg, partial,
+                       parts);
+    DMLC_HIP_CHECK_LAUNCH();
+    if (count > 0 && lc.pieces > 0 && spill_bins > 0) {
+      unsigned long long* const spill = reinterpret_cast<unsigned long long*>(partial + nw * parts);
+      const int64_t words = 2 * static_cast<int64_t>(nw) * spill_bins;
+      hipLaunchKernelGGL(k_gbdt_level_clear, dim3(GridFor(static_cast<uint64_t>(words), kThreads)),
+                         block, 0, stream, spill, words);
+      DMLC_HIP_CHECK_LAUNCH();
+      hipLaunchKernelGGL(k_gbdt_level_long_hist, dim3(static_cast<uint32_t>(lc.pieces)), block, 0,
+                         stream, m.offset, m.row, m.bin, nnz, m.cut_ptr, total, grad, hess, pos, rows,
+                         first, nodes, scale, lc.column, lc.bin_ptr, lc.piece_ptr, count, spill_bins,
+                         spill);
+      DMLC_HIP_CHECK_LAUNCH();
+      hipLaunchKernelGGL(k_gbdt_level_long_scan, dim3(long_parts, nw), block, 0, stream,
+                         reinterpret_cast<const long long*>(spill), m.cut_ptr, total, lc.column,
+                         lc.bin_ptr, count, spill_bins, lg, partial, parts,
+                         static_cast<int64_t>(segs));
+      DMLC_HIP_CHECK_LAUNCH();
+    } else if (long_parts > 0) {
+      // long columns without cuts: their slots hold no candidate
+      hipLaunchKernelGGL(k_gbdt_level_long_scan, dim3(long_parts, nw), block, 0, stream,
+                         static_cast<const long long*>(nullptr), m.cut_ptr, total, lc.column,
+                         lc.bin_ptr, count, spill_bins, lg, partial, parts,
+                         static_cast<int64_t>(segs));
+      DMLC_HIP_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(k_gbdt_split_pick, dim3(nw), block, 0, stream, partial, parts, feature + w0,
+                       bin + w0, default_left + w0, gain + w0);
+    DMLC_HIP_CHECK_LAUNCH();
+  }
 }
 
 void LaunchGbdtAdvance(const GbdtBinned& m, const int32_t* pos_in, const int64_t* feature,

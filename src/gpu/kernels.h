@@ -47,6 +47,7 @@
  *   GB3 / GB3m grad histogram LaunchGbdtHistogram (gbdt_kernels.hip)
  *   GB4 / GB4m best splits    LaunchGbdtBestSplits (gbdt_kernels.hip)
  *   GB5 advance rows     LaunchGbdtAdvance        (gbdt_kernels.hip)
+ *   GB9 fused level search LaunchGbdtLevelSplits, LaunchGbdtLongColumns (gbdt_kernels.hip)
  *   GB6 / GB6m forest inference LaunchForestPredict (forest_kernels.hip)
  * The launchers of K9, K11, M1 / M2, FF1 / FF2, G2, GB6 / GB6m and the transpose take
  * their CSR operand as one CsrView and pick the kernel for its index width
@@ -935,6 +936,49 @@ void LaunchGbdtBestSplits(const int64_t* hist, const int64_t* node_sum, const in
                           uint32_t num_outputs, double scale, double reg_lambda, double gamma,
                           double min_child_weight, void* scratch, int64_t* feature, int32_t* bin,
                           uint8_t* default_left, double* gain, hipStream_t stream);
+/*!
+ * \brief GB9: the columns of more than kGbdtSegmentEntries entries of a binned matrix, ascending:
+ *  column [count], bin_ptr [count + 1] (the running sum of their cut counts, ends at bins) and
+ *  piece_ptr [count + 1] (of their pieces of kGbdtSegmentEntries entries, ends at pieces).
+ *  count <= nnz / kGbdtSegmentEntries: these are the hot features.
+ */
+struct GbdtLongColumns {
+  const int64_t* column;
+  const int64_t* bin_ptr;
+  const int64_t* piece_ptr;
+  uint64_t count, bins, pieces;
+};
+/*! \brief GB9: fills the arrays of GbdtLongColumns (capacity >= nnz / kGbdtSegmentEntries columns,
+ *  capacity + 1 sums) and totals [3] = (count, bins, pieces), device words; one workgroup, once
+ *  per matrix */
+void LaunchGbdtLongColumns(const GbdtBinned& m, uint64_t capacity, int64_t* column, int64_t* bin_ptr,
+                           int64_t* piece_ptr, int64_t* totals, hipStream_t stream);
+/*!
+ * \brief GB9's scratch budget.  A level keeps 16 bytes per node and workgroup (nnz /
+ *  kGbdtSegmentEntries + 1 of them, plus one per 256 long columns) and a spill histogram of 16
+ *  bytes per node and bin of the long columns -- at most 256 nnz / kGbdtSegmentEntries bins, and
+ *  in practice the bins of a few hot features.  When all num_nodes of a level need more than this,
+ *  the launcher runs the level in consecutive windows of GbdtLevelWindowNodes nodes: more passes
+ *  over the entries, the same answer.  Only a single node's share can exceed the budget.
+ */
+constexpr size_t kGbdtLevelScratchBudget = size_t{256} << 20;
+/*! \brief nodes GB9 searches per pass over the matrix, in [1, num_nodes] */
+uint32_t GbdtLevelWindowNodes(uint64_t num_nodes, uint64_t nnz, const GbdtLongColumns& lc);
+/*! \brief bytes of 16-byte aligned scratch of LaunchGbdtLevelSplits */
+size_t GbdtLevelScratchBytes(uint64_t num_nodes, uint64_t nnz, const GbdtLongColumns& lc);
+/*!
+ * \brief GB9: the outputs of LaunchGbdtBestSplits on the histogram LaunchGbdtHistogram would
+ *  write for the same level (scalar layout), bit for bit, without that histogram.  A workgroup
+ *  per segment owns the columns of up to kGbdtSegmentEntries entries that start in it, sums them
+ *  in LDS and scans the sums there; longer columns go through the spill histogram in scratch.
+ *  node_sum [num_nodes x 2]; nnz, rows >= 1.
+ */
+void LaunchGbdtLevelSplits(const GbdtBinned& m, const GbdtLongColumns& lc, const float* grad,
+                           const float* hess, const int32_t* pos, int32_t first_node,
+                           uint32_t num_nodes, const int64_t* node_sum, double scale,
+                           double reg_lambda, double gamma, double min_child_weight, void* scratch,
+                           int64_t* feature, int32_t* bin, uint8_t* default_left, double* gain,
+                           hipStream_t stream);
 /*!
  * \brief GB5: pos_out[r] for every row: a row of node n = pos_in[r] -
  *  first_node in [0, num_nodes) goes to left[n] if feature[n] < 0, else by its

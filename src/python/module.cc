@@ -1392,6 +1392,50 @@ PYBIND11_MODULE(_dmlc, m) {
       py::arg("reg_lambda"), py::arg("gamma"), py::arg("min_child_weight"), py::arg("scratch"),
       py::arg("feature"), py::arg("bin"), py::arg("default_left"), py::arg("gain"),
       py::arg("stream"));
+  // GB9: the long columns travel as (column, bin_ptr, piece_ptr, count, bins, pieces)
+  using LongColumnsArg = std::tuple<uintptr_t, uintptr_t, uintptr_t, uint64_t, uint64_t, uint64_t>;
+  auto long_of = [](const LongColumnsArg& a) {
+    return gpu::GbdtLongColumns{Ptr<const int64_t>(std::get<0>(a)), Ptr<const int64_t>(std::get<1>(a)),
+                                Ptr<const int64_t>(std::get<2>(a)), std::get<3>(a), std::get<4>(a),
+                                std::get<5>(a)};
+  };
+  m.def(
+      "gbdt_long_columns",
+      [stream_of, binned_of](const BinnedArg& binned, uint64_t capacity, uintptr_t column,
+                             uintptr_t bin_ptr, uintptr_t piece_ptr, uintptr_t totals,
+                             uintptr_t stream) {
+        gpu::LaunchGbdtLongColumns(binned_of(binned), capacity, Ptr<int64_t>(column),
+                                   Ptr<int64_t>(bin_ptr), Ptr<int64_t>(piece_ptr),
+                                   Ptr<int64_t>(totals), stream_of(stream));
+      },
+      py::arg("binned"), py::arg("capacity"), py::arg("column"), py::arg("bin_ptr"),
+      py::arg("piece_ptr"), py::arg("totals"), py::arg("stream"));
+  m.def(
+      "gbdt_level_scratch_bytes",
+      [long_of](uint64_t num_nodes, uint64_t nnz, const LongColumnsArg& lc) {
+        return gpu::GbdtLevelScratchBytes(num_nodes, nnz, long_of(lc));
+      },
+      py::arg("num_nodes"), py::arg("nnz"), py::arg("long_columns"));
+  m.def(
+      "gbdt_level_splits",
+      [stream_of, binned_of, long_of](const BinnedArg& binned, const LongColumnsArg& lc,
+                                      uintptr_t grad, uintptr_t hess, uintptr_t pos,
+                                      int32_t first_node, uint32_t num_nodes, uintptr_t node_sum,
+                                      double scale, double reg_lambda, double gamma,
+                                      double min_child_weight, uintptr_t scratch, uintptr_t feature,
+                                      uintptr_t bin, uintptr_t default_left, uintptr_t gain,
+                                      uintptr_t stream) {
+        gpu::LaunchGbdtLevelSplits(
+            binned_of(binned), long_of(lc), Ptr<const float>(grad), Ptr<const float>(hess),
+            Ptr<const int32_t>(pos), first_node, num_nodes, Ptr<const int64_t>(node_sum), scale,
+            reg_lambda, gamma, min_child_weight, Ptr<void>(scratch), Ptr<int64_t>(feature),
+            Ptr<int32_t>(bin), Ptr<uint8_t>(default_left), Ptr<double>(gain), stream_of(stream));
+      },
+      py::arg("binned"), py::arg("long_columns"), py::arg("grad"), py::arg("hess"), py::arg("pos"),
+      py::arg("first_node"), py::arg("num_nodes"), py::arg("node_sum"), py::arg("scale"),
+      py::arg("reg_lambda"), py::arg("gamma"), py::arg("min_child_weight"), py::arg("scratch"),
+      py::arg("feature"), py::arg("bin"), py::arg("default_left"), py::arg("gain"),
+      py::arg("stream"));
   m.def(
       "gbdt_advance",
       [stream_of, binned_of](const BinnedArg& binned, uintptr_t pos_in, uintptr_t feature,
